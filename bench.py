@@ -17,10 +17,16 @@ see DESIGN.md "decode roofline" for how the seam is accounted).  A step =
 one batch of --clips clips.  Multi-GPU = weak scaling: each rank processes
 its own clips; no data-path collective.
 
-Contract: one JSON line from rank 0 with metric/value/unit/... plus
-`roofline` (dominant kernel = gemm_bf16, HIP-event timed on its launch
-stream inside the timed region) and `cpu_baseline` (oracle timed on host
-cores, rank 0, N=1 only).
+Contract: one JSON line from rank 0 with metric/value/unit/ms_per_step/...
+A plain run does only what that line needs: set up, warm up, time --steps
+steps, write --dump-outputs if asked, print.  --full adds the legs that
+take runs of their own: `roofline` (dominant kernel = gemm_bf16, HIP-event
+timed per launch on its stream in extra eager steps after the timed
+region) and `cpu_baseline` (oracle timed on host cores, rank 0, N=1 only).
+
+--dump-outputs DIR writes what the last timed step returned to its caller,
+the (clips, proj) f32 clip embeddings, as DIR/clip_embeddings.npy.  Inputs
+are seeded, so equal arguments give equal inputs from run to run.
 """
 
 from __future__ import annotations
@@ -130,12 +136,24 @@ def main() -> None:
         "host-buffers rate; reported as its own line, never the headline "
         "value — tier contract / DESIGN.md §4)",
     )
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument(
+        "--full", action="store_true",
+        help="after the timed steps also run the roofline leg (per-launch "
+        "HIP-event timing of gemm_bf16) and the CPU-oracle baseline, and "
+        "add `roofline` / `cpu_baseline` to the result line",
+    )
+    ap.add_argument(
+        "--dump-outputs", metavar="DIR", default=None,
+        help="write the last timed step's clip embeddings (float32) to "
+        "DIR/clip_embeddings.npy (rank r > 0: clip_embeddings_rank<r>.npy)",
+    )
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU-oracle baseline out")
     ap.add_argument(
         "--graphs", action="store_true", default=True,
         help="capture the per-step kernel sequence in a hipGraph and replay it "
         "(launch-bound inner loop -> graph, per the MI355X design brief); "
-        "the roofline leg still runs eager with HIP-event timing",
+        "the --full roofline leg still runs eager with HIP-event timing",
     )
     ap.add_argument("--no-graphs", dest="graphs", action="store_false")
     ap.add_argument(
@@ -151,6 +169,8 @@ def main() -> None:
         "SigLIP-L class)",
     )
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank = int(os.environ.get("RANK", 0))
@@ -253,7 +273,7 @@ def main() -> None:
 
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last_out = step()
     torch.cuda.synchronize(device)
     if dist:
         dist.barrier()
@@ -263,31 +283,44 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # roofline leg: HIP-event per-launch timing of the dominant kernel, on
-    # its launch stream (eager; graphs cannot carry per-launch events)
-    hotpath.timing_enable(True)
-    roofline_steps = max(2, args.steps // 5)
-    for _ in range(roofline_steps):
-        step_device().cpu()
-    torch.cuda.synchronize(device)
-    hotpath.timing_enable(False)
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "clip_embeddings" + (f"_rank{rank}" if rank else "") + ".npy"
+        np.save(os.path.join(args.dump_outputs, name),
+                np.ascontiguousarray(last_out, dtype=np.float32))
 
-    gemm_ms, gemm_count = hotpath.timing_report("gemm_bf16")
     total_clips = B * args.steps * world
     clips_per_s = total_clips / elapsed
     frames_per_s = clips_per_s * FRAMES_PER_CLIP
 
-    gemm_flops_step = gemm_flops_per_frame(args.model) * F
-    gemm_flops_total = gemm_flops_step * roofline_steps  # instrumented phase
-    achieved = gemm_flops_total / (gemm_ms / 1e3) if gemm_ms > 0 else 0.0
-    peak = 2.5e15  # dense bf16 MFMA peak, MI355X_MICROARCH.md (spec; 2495 TF measured)
+    if args.full:
+        # roofline leg: HIP-event per-launch timing of the dominant kernel, on
+        # its launch stream (eager; graphs cannot carry per-launch events)
+        hotpath.timing_enable(True)
+        roofline_steps = max(2, args.steps // 5)
+        for _ in range(roofline_steps):
+            step_device().cpu()
+        torch.cuda.synchronize(device)
+        hotpath.timing_enable(False)
+
+        gemm_ms, gemm_count = hotpath.timing_report("gemm_bf16")
+        gemm_flops_step = gemm_flops_per_frame(args.model) * F
+        gemm_flops_total = gemm_flops_step * roofline_steps  # instrumented phase
+        achieved = gemm_flops_total / (gemm_ms / 1e3) if gemm_ms > 0 else 0.0
+        peak = 2.5e15  # MI355X dense bf16 MFMA peak (spec; 2495 TF measured)
+        roofline = {
+            "bound": "mfma",
+            "achieved": round(achieved, 3),
+            "peak": peak,
+            "unit": "FLOP/s",
+            "frac": round(achieved / peak, 4),
+            "traffic": None,
+            "kernel": "gemm_bf16",
+            "launches": int(gemm_count),
+            "kernel_ms_total": round(gemm_ms, 3),
+        }
 
     if rank == 0:
-        cpu_baseline = (
-            None
-            if (args.skip_cpu_baseline or world > 1)
-            else run_cpu_baseline()
-        )
         out = {
             "metric": "clips/sec + embedded frames/sec, 1080p30 H.264, 1/2/4/8 MI355X",
             "value": round(clips_per_s, 3),
@@ -315,19 +348,14 @@ def main() -> None:
                 "parallelism": f"dp{world}",
                 "embedded_frames_per_s": round(frames_per_s, 1),
             },
-            "roofline": {
-                "bound": "mfma",
-                "achieved": round(achieved, 3),
-                "peak": peak,
-                "unit": "FLOP/s",
-                "frac": round(achieved / peak, 4),
-                "traffic": None,
-                "kernel": "gemm_bf16",
-                "launches": int(gemm_count),
-                "kernel_ms_total": round(gemm_ms, 3),
-            },
-            "cpu_baseline": cpu_baseline,
         }
+        if args.full:
+            out["roofline"] = roofline
+            out["cpu_baseline"] = (
+                None
+                if (args.skip_cpu_baseline or world > 1)
+                else run_cpu_baseline()
+            )
         print(json.dumps(out))
     if dist:
         dist.destroy_process_group()

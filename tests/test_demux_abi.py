@@ -15,6 +15,7 @@ import pytest
 
 from cosmos_curate_amd import build as cc_build
 from cosmos_curate_amd import hotpath
+from golden_videos import video_bytes
 from oracle import mp4_demux, mp4_write
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
@@ -48,14 +49,8 @@ def test_hip_unavailable_is_loud(built_lib):
 def test_demux_parity_sintel_goldens(built_lib, golden_dir):
     pts_golden = np.load(golden_dir / "sintel_pts.npz")
     meta = json.loads((golden_dir / "sintel_meta.json").read_text())
-    ref_dir = pathlib.Path("/root/reference/tests/cosmos_curate/pipelines/video/data")
     for key in ["test_clip_10s", "test_video_30s"]:
-        # On the GPU box /root/reference is absent: fall back to checking the
-        # committed golden PTS against the synth fixture only.
-        src = ref_dir / f"{key}.mp4"
-        if not src.exists():
-            pytest.skip("reference fixtures not present (GPU box)")
-        data = src.read_bytes()
+        data = video_bytes(key)  # sample 0 is kept whole in the fixture
         with hotpath.Demuxer(data) as d:
             info = d.probe()
             got = d.timestamps()

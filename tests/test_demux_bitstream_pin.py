@@ -13,44 +13,26 @@ the container tables never touch:
   * VUI fps (when present)  ==  stts-derived average fps
   * frame_num continuity sanity on the decode-order walk
 
-Runs on the reference's own AVC fixtures (test_clip_10s.mp4,
-test_video_30s.mp4) when the reference tree is present (dev container),
-and always on the committed synthetic B-frame fixture.
+Runs on the committed real-AVC fixtures (tests/golden_videos.py: the
+reference's test_clip_10s / test_video_30s and the ffmpeg samples
+cockatoo / realshort, slice payload blanked past the headers).
 """
 
 from __future__ import annotations
 
-import pathlib
-
 import numpy as np
 import pytest
 
+from golden_videos import NAMES, video_bytes
 from oracle import h264_bitstream as bs
 from oracle import mp4_demux
 
-GOLDEN = pathlib.Path(__file__).parent / "golden"
-REF_DATA = pathlib.Path(
-    "/root/reference/tests/cosmos_curate/pipelines/video/data")
-
-
-IMAGEIO_RES = pathlib.Path(
-    "/opt/conda/lib/python3.9/site-packages/imageio/resources/images")
-
-
-def _fixtures() -> list[pathlib.Path]:
-    # real AVC elementary streams only (synth_bframes.mp4 carries fake
-    # payloads for container-level tests and has no parsable slices).
-    # cockatoo.mp4 (imageio sample, in-image) is the load-bearing case:
-    # a real ffmpeg B-frame stream (275/280 nonzero ctts entries, 59
-    # reordered positions) — exactly the reordering the VERDICT asked to
-    # pin externally.
-    if not REF_DATA.is_dir():
-        return []
-    out = [REF_DATA / "test_clip_10s.mp4", REF_DATA / "test_video_30s.mp4"]
-    for name in ("cockatoo.mp4", "realshort.mp4"):
-        if (IMAGEIO_RES / name).is_file():
-            out.append(IMAGEIO_RES / name)
-    return out
+# real AVC elementary streams only (synth_bframes.mp4 carries fake
+# payloads for container-level tests and has no parsable slices).
+# cockatoo is the load-bearing case: a real ffmpeg B-frame stream
+# (275/280 nonzero ctts entries, 59 reordered positions) — exactly the
+# reordering the VERDICT asked to pin externally.
+FIXTURES = list(NAMES)
 
 
 def _segment_order_check(ticks, pocs_idr, name):
@@ -71,29 +53,23 @@ def _segment_order_check(ticks, pocs_idr, name):
     return reordered_total
 
 
-pytestmark = pytest.mark.skipif(
-    not REF_DATA.is_dir(),
-    reason="reference AVC fixtures absent (GPU box); pin runs in the CPU suite",
-)
-
-
-@pytest.mark.parametrize("path", _fixtures(), ids=lambda p: p.stem)
-def test_poc_display_order_matches_ctts_pts(path):
-    data = path.read_bytes()
+@pytest.mark.parametrize("name", FIXTURES)
+def test_poc_display_order_matches_ctts_pts(name):
+    data = video_bytes(name)
     trk = mp4_demux.parse_mp4(data)[0]
     pkts = mp4_demux.annexb_packets(data, trk)
     ticks = trk.pts
     pocs_idr = bs.access_unit_pocs_idr(pkts)
     assert len(pocs_idr) == len(ticks)
-    reordered = _segment_order_check(ticks, pocs_idr, path.name)
-    if path.name == "cockatoo.mp4":
+    reordered = _segment_order_check(ticks, pocs_idr, name)
+    if name == "cockatoo":
         # the B-frame case must actually exercise reordering
         assert reordered >= 50, reordered
 
 
-@pytest.mark.parametrize("path", _fixtures(), ids=lambda p: p.stem)
-def test_sps_geometry_and_fps_match_container(path):
-    data = path.read_bytes()
+@pytest.mark.parametrize("name", FIXTURES)
+def test_sps_geometry_and_fps_match_container(name):
+    data = video_bytes(name)
     trk = mp4_demux.parse_mp4(data)[0]
     pkts = mp4_demux.annexb_packets(data, trk)[:4]
     sps = bs.sps_of_packets(pkts)
@@ -109,10 +85,7 @@ def test_bitstream_parser_on_c_abi_packets():
     order — the pin holds through the C ABI, not just the oracle."""
     from cosmos_curate_amd import hotpath
 
-    path = (IMAGEIO_RES / "cockatoo.mp4"
-            if (IMAGEIO_RES / "cockatoo.mp4").is_file()
-            else REF_DATA / "test_video_30s.mp4")
-    data = path.read_bytes()
+    data = video_bytes("cockatoo")
     with hotpath.Demuxer(data) as d:
         info = d.probe()
         pkts, ticks = [], []
@@ -121,17 +94,14 @@ def test_bitstream_parser_on_c_abi_packets():
             pkts.append(pkt)
             ticks.append(pts)
     _segment_order_check(ticks, bs.access_unit_pocs_idr(pkts),
-                         "c-abi:" + path.name)
+                         "c-abi:cockatoo")
 
 
 def test_pin_catches_ctts_corruption():
     """Negative control: corrupt one ctts entry of the real B-frame
     stream and the POC pin must DETECT the divergence — evidence the
     cross-check has teeth, not just vacuous agreement."""
-    path = IMAGEIO_RES / "cockatoo.mp4"
-    if not path.is_file():
-        pytest.skip("cockatoo fixture not present")
-    data = bytearray(path.read_bytes())
+    data = bytearray(video_bytes("cockatoo"))
     i = bytes(data).find(b"ctts")
     assert i > 0, "fixture has no ctts box"
     # ctts box: size(4) type(4) ver/flags(4) entry_count(4) then

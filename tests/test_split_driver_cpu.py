@@ -166,17 +166,12 @@ def test_mp4_transcode_stream_copy_and_sync_guard(golden_dir):
 
 def test_mp4_remux_sintel_head_span(golden_dir):
     """Reference fixture (single-IDR): [0,10 s) span copies sample-exact."""
-    import pathlib
-
     from cosmos_curate_amd import hotpath
+    from golden_videos import video_bytes
     from oracle import mp4_demux
 
-    src_path = pathlib.Path(
-        "/root/reference/tests/cosmos_curate/pipelines/video/data/test_video_30s.mp4"
-    )
-    if not src_path.exists():
-        pytest.skip("reference fixtures not present (GPU box)")
-    data = src_path.read_bytes()
+    # samples 0, 100 and 239 are kept whole in the committed fixture
+    data = video_bytes("test_video_30s")
     src = mp4_demux.parse_mp4(data)[0]
     with hotpath.Demuxer(data) as d:
         clip = d.remux_clip(0.0, 10.0)
