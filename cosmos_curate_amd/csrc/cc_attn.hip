@@ -11,6 +11,8 @@
 //                 rows), LDS only V^T + P -> 2 WG/CU;
 //   k_attn_flash  seq > 288 (SigLIP-384-class): K/V streamed in 64-row
 //                 tiles with online softmax, O rescaled flash-style.
+// Plus k_attn_cls (any seq): one query row per (frame, head) for the
+// last layer of a CLS-pooled tower — separate q, strided K/V, O [n, H].
 //
 // Numerics (all rungs): f32 accumulation and softmax (matches sdpa's
 // f32 softmax on bf16 inputs); probabilities round to bf16 before PV,
@@ -510,7 +512,148 @@ __global__ __launch_bounds__(256, 2) void k_attn_flash(
   }
 }
 
+// ---- CLS-query variant: one query row per (frame, head) ----
+// The last encoder layer of a CLS-pooled tower needs attention only for
+// token 0 of each frame (post-LN and the projection read nothing else),
+// but every token still serves as a key and a value.  With one query row
+// MFMA buys nothing; the kernel is a bandwidth pass over K and V, read
+// in place from the K/V GEMM output through a common row stride.
+//
+// One wave per (frame, head), four waves per workgroup, no LDS and no
+// barriers.  Keys stream in 64-row chunks; lane (jg = lane>>3, dg =
+// lane&7) owns keys j = 8*jj + jg (jj = 0..7) and the 8 dims
+// [8*dg, 8*dg+8): every load instruction fetches eight full 128-byte
+// K (or V) rows, 16 bytes per lane.  q.K partial dots reduce across the
+// 8 dg lanes; the score of key 8*jj+jg then already sits in the lanes
+// that multiply it into V, so P.V needs no exchange.  Online softmax
+// across chunks exactly as k_attn_flash (f32 running max/sum,
+// unnormalized probabilities rounded to bf16 before PV, O / l at the
+// end); the cross-lane reductions run in a fixed order, no atomics ->
+// bit-identical from run to run.
+__global__ __launch_bounds__(256) void k_attn_cls(
+    const __bf16* __restrict__ q, const __bf16* __restrict__ k,
+    const __bf16* __restrict__ v, long ldkv, __bf16* __restrict__ out,
+    long n_frames, int seq, int heads, int hidden, float scale) {
+  const int lane = threadIdx.x & 63;
+  const long fh = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (fh >= n_frames * heads) return;  // whole wave; no barriers below
+  const long frame = fh / heads;
+  const int head = (int)(fh % heads);
+  const int jg = lane >> 3;
+  const int dg = lane & 7;
+
+  float qf[8];
+  {
+    const bf16x8 q8 =
+        *(const bf16x8*)(q + frame * (long)hidden + head * HD + dg * 8);
+#pragma unroll
+    for (int e = 0; e < 8; e++) qf[e] = (float)q8[e] * scale;
+  }
+  const long kv_base = frame * (long)seq * ldkv + (long)head * HD + dg * 8;
+
+  float m_run = -1e30f, l_run = 0.0f;
+  float oacc[8] = {};
+  for (int k0 = 0; k0 < seq; k0 += 64) {
+    // all 16 row loads of the chunk up front (V does not wait for the
+    // softmax); rows past seq clamp to seq-1 and are masked below
+    bf16x8 kr[8], vr[8];
+#pragma unroll
+    for (int jj = 0; jj < 8; jj++) {
+      int j = k0 + jj * 8 + jg;
+      j = j < seq ? j : seq - 1;
+      kr[jj] = *(const bf16x8*)(k + kv_base + (long)j * ldkv);
+      vr[jj] = *(const bf16x8*)(v + kv_base + (long)j * ldkv);
+    }
+    float s[8];
+    float mx = m_run;
+#pragma unroll
+    for (int jj = 0; jj < 8; jj++) {
+      float d = 0.0f;
+#pragma unroll
+      for (int e = 0; e < 8; e++) d += qf[e] * (float)kr[jj][e];
+      d += __shfl_xor(d, 1);
+      d += __shfl_xor(d, 2);
+      d += __shfl_xor(d, 4);
+      if (k0 + jj * 8 + jg >= seq) d = -1e30f;
+      s[jj] = d;
+      mx = fmaxf(mx, d);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 8));
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float alpha = __expf(m_run - mx);
+    float sum = 0.0f;
+    float pv[8] = {};
+#pragma unroll
+    for (int jj = 0; jj < 8; jj++) {
+      const bool live = k0 + jj * 8 + jg < seq;
+      const float e = live ? __expf(s[jj] - mx) : 0.0f;
+      sum += e;
+      const float p = (float)(__bf16)e;  // bf16 probabilities before PV
+#pragma unroll
+      for (int d = 0; d < 8; d++)
+        pv[d] += live ? p * (float)vr[jj][d] : 0.0f;
+    }
+    sum += __shfl_xor(sum, 8);
+    sum += __shfl_xor(sum, 16);
+    sum += __shfl_xor(sum, 32);
+    l_run = l_run * alpha + sum;
+    m_run = mx;
+#pragma unroll
+    for (int d = 0; d < 8; d++) oacc[d] = oacc[d] * alpha + pv[d];
+  }
+  // fold the 8 key groups (fixed order), normalize, one 16-byte store
+  // per dim group
+#pragma unroll
+  for (int d = 0; d < 8; d++) {
+    float o = oacc[d];
+    o += __shfl_xor(o, 8);
+    o += __shfl_xor(o, 16);
+    o += __shfl_xor(o, 32);
+    oacc[d] = o;
+  }
+  if (jg == 0) {
+    const float inv = 1.0f / l_run;
+    bf16x8 o8;
+#pragma unroll
+    for (int d = 0; d < 8; d++) o8[d] = (__bf16)(oacc[d] * inv);
+    *(bf16x8*)(out + frame * (long)hidden + head * HD + dg * 8) = o8;
+  }
+}
+
 }  // namespace
+
+extern "C" int cc_attn_cls(const void* q, const void* k, const void* v,
+                           int64_t ldkv, void* out, int64_t n_frames, int seq,
+                           int heads, int hidden, float scale,
+                           uint64_t stream) {
+  if (!q || !k || !v || !out || n_frames <= 0 || seq <= 0 || heads <= 0)
+    return cc::set_error(CC_ERR_INVALID, "bad attn_cls args");
+  if (hidden != heads * HD)
+    return cc::set_error(CC_ERR_UNSUPPORTED, "cc_attn_cls needs hd == 64");
+  // 16-byte row loads: stride and bases must keep every row 16B-aligned
+  if (ldkv < hidden || ldkv % 8 != 0 || ((uintptr_t)q & 15) ||
+      ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15))
+    return cc::set_error(CC_ERR_INVALID,
+                         "cc_attn_cls needs ldkv >= hidden, ldkv %% 8 == 0 "
+                         "and 16-byte aligned q/k/v/out");
+  const int64_t nwave = n_frames * heads;
+  if ((nwave + 3) / 4 > 0x7fffffffLL)
+    return cc::set_error(CC_ERR_INVALID, "attn_cls grid too large");
+  dim3 block(256), grid((unsigned)((nwave + 3) / 4));
+  hipEvent_t ev0, ev1;
+  bool timed = cc::timed_begin(stream, &ev0, &ev1);
+  hipLaunchKernelGGL(k_attn_cls, grid, block, 0, (hipStream_t)stream,
+                     (const __bf16*)q, (const __bf16*)k, (const __bf16*)v,
+                     (long)ldkv, (__bf16*)out, (long)n_frames, seq, heads,
+                     hidden, scale);
+  hipError_t e = hipGetLastError();
+  if (timed) cc::timed_end("attn_cls", stream, ev0, ev1);
+  if (e != hipSuccess)
+    return cc::set_error(CC_ERR_HIP, "attn_cls launch: %s",
+                         hipGetErrorString(e));
+  return CC_OK;
+}
 
 extern "C" int cc_attn_small(const void* qkv, void* out, int64_t n_frames,
                              int seq, int heads, int hidden, float scale,

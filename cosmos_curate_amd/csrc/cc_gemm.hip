@@ -107,12 +107,16 @@ __device__ __forceinline__ bf16x8 frag_read(const __bf16* tile, int row,
   return *(const bf16x8*)(tile + (long)row * BK + slot * 8);
 }
 
+// lda / ldr: row strides (elements) of A and of the residual — K and N
+// for dense operands; larger when the rows are a strided subset of a
+// bigger tensor (the CLS rows of [frames*seq, hidden]).  B and C are
+// always dense.
 template <int ACT, bool HAS_BIAS, bool HAS_RES>  // ACT 1 = quick-gelu
 __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
     const __bf16* __restrict__ A, const __bf16* __restrict__ B,
     void* __restrict__ C, const float* __restrict__ bias,
-    const __bf16* __restrict__ residual, long M, long N, long K,
-    int c_is_bf16, int nbx, int nwg, int do_remap) {
+    const __bf16* __restrict__ residual, long M, long N, long K, long lda,
+    long ldr, int c_is_bf16, int nbx, int nwg, int do_remap) {
   __shared__ __bf16 lds[2 * (BM + BN) * BK];  // one __shared__ object (G16 4a)
 #define AS(b) (lds + (b) * (BM * BK))
 #define BS(b) (lds + 2 * (BM * BK) + (b) * (BN * BK))
@@ -140,7 +144,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
   f32x4 acc[MFR][NFR] = {};
 
   const long KT = K / BK;
-  stage_slice(A, K, arow0, M, 0, AS(0) + 32 * wid * BK, lane);
+  stage_slice(A, lda, arow0, M, 0, AS(0) + 32 * wid * BK, lane);
   stage_slice(B, K, brow0, N, 0, BS(0) + 32 * wid * BK, lane);
 
   const int arow_frag = waveM * WM + (lane & 15);
@@ -170,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
     }
     if (kt + 1 < KT) {
       const long k0 = (kt + 1) * BK;
-      stage_slice(A, K, arow0, M, k0, AS(buf ^ 1) + 32 * wid * BK, lane);
+      stage_slice(A, lda, arow0, M, k0, AS(buf ^ 1) + 32 * wid * BK, lane);
       stage_slice(B, K, brow0, N, k0, BS(buf ^ 1) + 32 * wid * BK, lane);
     }
 #pragma unroll
@@ -205,7 +209,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
         if constexpr (HAS_RES) {
 #pragma unroll
           for (int r = 0; r < 4; r++)
-            rv[r] = (float)residual[(crow_base + m * FRAG + r) * N + col];
+            rv[r] = (float)residual[(crow_base + m * FRAG + r) * ldr + col];
         }
 #pragma unroll
         for (int r = 0; r < 4; r++) {
@@ -250,7 +254,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
           float t = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * z) + 1.0f);
           v = 0.5f * v * (1.0f + t);
         }
-        if constexpr (HAS_RES) v += (float)residual[row * N + col];
+        if constexpr (HAS_RES) v += (float)residual[row * ldr + col];
         if (c_is_bf16)
           ((unsigned short*)C)[row * N + col] = f32_to_bf16_rne(v);
         else
@@ -751,18 +755,33 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
 #undef KTILE2
 }
 
-}  // namespace
-
-extern "C" int cc_gemm_bf16_ex(const void* A, const void* B, void* C,
-                               int64_t M, int64_t N, int64_t K,
-                               const float* bias, int c_dtype, int act,
-                               const void* residual, uint64_t stream) {
+// Shared launcher.  lda / ldr are the row strides (elements) of A and of
+// the residual; a launch with lda != K or ldr != N is "strided" and
+// always runs the 128-tile body, the only one that carries the strides
+// (the persistent 256² loop stays dense: it is the hot kernel and the
+// strided launches are the small M = frames ones).
+int gemm_launch(const void* A, int64_t lda, const void* B, void* C, int64_t M,
+                int64_t N, int64_t K, const float* bias, int c_dtype, int act,
+                const void* residual, int64_t ldr, uint64_t stream) {
   if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0)
     return cc::set_error(CC_ERR_INVALID, "bad gemm args");
   if (K % BK != 0)
     return cc::set_error(CC_ERR_UNSUPPORTED,
                          "cc_gemm_bf16 requires K %% 64 == 0 (got %lld)",
                          (long long)K);
+  if (!residual) ldr = N;
+  if (lda < K || ldr < N)
+    return cc::set_error(CC_ERR_INVALID,
+                         "gemm row stride below row length (lda %lld < K "
+                         "%lld or ldr %lld < N %lld)",
+                         (long long)lda, (long long)K, (long long)ldr,
+                         (long long)N);
+  if (lda % 8 != 0)
+    return cc::set_error(CC_ERR_INVALID,
+                         "gemm lda %lld breaks the 16-byte alignment of the "
+                         "direct-to-LDS loads (needs lda %% 8 == 0)",
+                         (long long)lda);
+  const bool strided = lda != K || ldr != N;
   int nbx = (int)((N + BN - 1) / BN);
   int nby = (int)((M + BM - 1) / BM);
   int nwg = nbx * nby;
@@ -779,7 +798,7 @@ extern "C" int cc_gemm_bf16_ex(const void* A, const void* B, void* C,
     const char* e = getenv("CC_GEMM_WIDE");
     return e ? atoi(e) : -1;
   }();
-  const bool wide = wide_env >= 0 ? wide_env != 0 : false;
+  const bool wide = !strided && (wide_env >= 0 ? wide_env != 0 : false);
   // 256² 8-phase template for the shapes its halved A/B re-read traffic
   // pays on (measured profiles/r01_v10_b64.log: wins every shape with
   // K>=1536 or N>=1536; loses only N=768 && K=768 at large M).
@@ -797,10 +816,20 @@ extern "C" int cc_gemm_bf16_ex(const void* A, const void* B, void* C,
   const int nbx2 = (int)((N + BN2 - 1) / BN2);
   const int nby2 = (int)((M + BM2 - 1) / BM2);
   const int nwg2 = nbx2 * nby2;
+  // Exception for the K-trigger at M = frames (the CLS-only last layer's
+  // fc2, N 768 / K 3072 at M 4704): 57 256-tiles leave most of the fleet
+  // idle where the 128 body has 222 tiles — measured 67.1 vs 53.1 us per
+  // launch, and 84.8 vs 67.6 us at the L/14 shape (76 vs 296 tiles),
+  // profiles/r03_gemm_small_m_ab.log.  Kept narrow: only when the
+  // 256-grid fills under half the fleet while the 128-grid fills at
+  // least half.  The N-trigger stays: fc1 at the same M (228 / 304
+  // 256-tiles) measured faster on the 256 body (29.7 vs 41.2 us).
+  const bool underfill = N < 1536 && nwg2 < 128 && nwg >= 128;
   const bool t256 =
-      !wide && t256_ok &&
-      (tile_env >= 0 ? tile_env != 0
-                     : (K >= 1536 || N >= 1536 || nwg2 >= 256));
+      !wide && !strided && t256_ok &&
+      (tile_env >= 0
+           ? tile_env != 0
+           : ((K >= 1536 && !underfill) || N >= 1536 || nwg2 >= 256));
   const bool hb = bias != nullptr;
   const bool hr = residual != nullptr;
   // XCD remap only for outputs that spill L3 (measured negative on the
@@ -843,6 +872,13 @@ extern "C" int cc_gemm_bf16_ex(const void* A, const void* B, void* C,
                      (const __bf16*)A, (const __bf16*)B, C, bias,             \
                      (const __bf16*)residual, (long)M, (long)N, (long)K,      \
                      c_dtype == 1 ? 1 : 0, nbx, nwg, remap)
+  // the 128-tile 16x16x32 body also takes the row strides
+#define CC_LAUNCH_GEMM_LD(KER, A_, HB, HR)                                    \
+  hipLaunchKernelGGL((KER<A_, HB, HR>), grid, block, 0, (hipStream_t)stream,  \
+                     (const __bf16*)A, (const __bf16*)B, C, bias,             \
+                     (const __bf16*)residual, (long)M, (long)N, (long)K,      \
+                     (long)lda, (long)ldr, c_dtype == 1 ? 1 : 0, nbx, nwg,    \
+                     remap)
 #define CC_LAUNCH_T256(A_, HB, HR)                                            \
   do {                                                                        \
     if (epi_staged)                                                           \
@@ -858,21 +894,21 @@ extern "C" int cc_gemm_bf16_ex(const void* A, const void* B, void* C,
                          (long)M, (long)N, (long)K, c_dtype == 1 ? 1 : 0,     \
                          nbx, nwg, remap);                                    \
   } while (0)
-#define CC_DISPATCH_ACT(KER, A_)                                              \
+#define CC_DISPATCH_ACT(L, KER, A_)                                           \
   do {                                                                        \
-    if (hb && hr) CC_LAUNCH_GEMM(KER, A_, true, true);                        \
-    else if (hb) CC_LAUNCH_GEMM(KER, A_, true, false);                        \
-    else if (hr) CC_LAUNCH_GEMM(KER, A_, false, true);                        \
-    else CC_LAUNCH_GEMM(KER, A_, false, false);                               \
+    if (hb && hr) L(KER, A_, true, true);                                     \
+    else if (hb) L(KER, A_, true, false);                                     \
+    else if (hr) L(KER, A_, false, true);                                     \
+    else L(KER, A_, false, false);                                            \
   } while (0)
-#define CC_DISPATCH(KER)                                                      \
+#define CC_DISPATCH(L, KER)                                                   \
   do {                                                                        \
-    if (act == 1) CC_DISPATCH_ACT(KER, 1);                                    \
-    else if (act == 2) CC_DISPATCH_ACT(KER, 2);  /* tanh-gelu (SigLIP) */     \
-    else CC_DISPATCH_ACT(KER, 0);                                             \
+    if (act == 1) CC_DISPATCH_ACT(L, KER, 1);                                 \
+    else if (act == 2) CC_DISPATCH_ACT(L, KER, 2);  /* tanh-gelu (SigLIP) */  \
+    else CC_DISPATCH_ACT(L, KER, 0);                                          \
   } while (0)
   if (wide)
-    CC_DISPATCH(k_gemm_bf16_w32);
+    CC_DISPATCH(CC_LAUNCH_GEMM, k_gemm_bf16_w32);
   else if (t256) {
 #define CC_DISPATCH_ACT_T256(A_)                                              \
   do {                                                                        \
@@ -886,15 +922,35 @@ extern "C" int cc_gemm_bf16_ex(const void* A, const void* B, void* C,
     else CC_DISPATCH_ACT_T256(0);
 #undef CC_DISPATCH_ACT_T256
   } else
-    CC_DISPATCH(k_gemm_bf16);
+    CC_DISPATCH(CC_LAUNCH_GEMM_LD, k_gemm_bf16);
 #undef CC_DISPATCH
 #undef CC_DISPATCH_ACT
 #undef CC_LAUNCH_GEMM
+#undef CC_LAUNCH_GEMM_LD
   hipError_t e = hipGetLastError();
   if (timed) cc::timed_end("gemm_bf16", stream, ev0, ev1);
   if (e != hipSuccess)
     return cc::set_error(CC_ERR_HIP, "gemm launch: %s", hipGetErrorString(e));
   return CC_OK;
+}
+
+}  // namespace
+
+extern "C" int cc_gemm_bf16_ex(const void* A, const void* B, void* C,
+                               int64_t M, int64_t N, int64_t K,
+                               const float* bias, int c_dtype, int act,
+                               const void* residual, uint64_t stream) {
+  return gemm_launch(A, K, B, C, M, N, K, bias, c_dtype, act, residual, N,
+                     stream);
+}
+
+extern "C" int cc_gemm_bf16_strided(const void* A, int64_t lda, const void* B,
+                                    void* C, int64_t M, int64_t N, int64_t K,
+                                    const float* bias, int c_dtype, int act,
+                                    const void* residual, int64_t ldr,
+                                    uint64_t stream) {
+  return gemm_launch(A, lda, B, C, M, N, K, bias, c_dtype, act, residual, ldr,
+                     stream);
 }
 
 extern "C" int cc_gemm_bf16(const void* A, const void* B, void* C, int64_t M,

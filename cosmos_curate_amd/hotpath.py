@@ -82,7 +82,14 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.cc_gemm_bf16_ex.argtypes = [
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64,
         c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_uint64]
+    lib.cc_gemm_bf16_strided.argtypes = [
+        c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
+        c.c_int64, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_int64,
+        c.c_uint64]
 
+    lib.cc_attn_cls.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64,
+        c.c_int, c.c_int, c.c_int, c.c_float, c.c_uint64]
     lib.cc_attn_small.argtypes = [
         c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int, c.c_int,
         c.c_float, c.c_uint64]

@@ -12,7 +12,9 @@ visual projection), organized the MI355X way:
 - attention softmax/bmm and layernorms stay on torch-rocm
   (north_star: "the rest stays torch-rocm"); layernorms compute in f32;
 - activations are bf16 end-to-end; the final embedding is cast to f32 and
-  L2-normalized (clip.py:74).
+  L2-normalized (clip.py:74);
+- the last encoder layer computes only what the CLS pooling reads: K/V
+  for every token, everything else for the CLS rows.
 
 No CPU fallback: _linear() requires the HIP extension + a GPU (the tests
 may monkeypatch _linear to torch on CPU to pin arithmetic structure; the
@@ -39,26 +41,57 @@ def _cc_linear(
 ) -> torch.Tensor:
     """C[M,N] = act(x[M,K] @ w[N,K]^T + bias) [+ residual], bf16 out.
 
-    act 1 = quick-gelu; residual fused into the epilogue (cc_gemm_bf16_ex)."""
+    act 1 = quick-gelu; residual fused into the epilogue (cc_gemm_bf16_ex).
+
+    x and residual may be row-strided 2-D views (unit column stride, e.g.
+    the CLS rows ``t[:, 0]`` of a [n, seq, H] tensor): the kernel reads
+    them in place through cc_gemm_bf16_strided — no gather copy."""
     lib = hotpath.require_gpu()
     assert x.dtype == torch.bfloat16 and w_bf16.dtype == torch.bfloat16
-    x = x.contiguous()
+    assert w_bf16.is_contiguous()
     M, K = x.shape
     N = w_bf16.shape[0]
+    lda = _row_stride(x)
+    if lda is None or lda % 8 != 0:
+        x = x.contiguous()
+        lda = K
     out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
     stream = torch.cuda.current_stream(x.device).cuda_stream
+    ldr = N
     if residual is not None:
-        residual = residual.contiguous()
         assert residual.shape == out.shape and residual.dtype == torch.bfloat16
-    hotpath.check(
-        lib.cc_gemm_bf16_ex(
-            x.data_ptr(), w_bf16.data_ptr(), out.data_ptr(), M, N, K,
-            bias_f32.data_ptr() if bias_f32 is not None else None,
-            1, act, residual.data_ptr() if residual is not None else None,
-            stream,
+        ldr = _row_stride(residual)
+        if ldr is None:
+            residual = residual.contiguous()
+            ldr = N
+    bias_p = bias_f32.data_ptr() if bias_f32 is not None else None
+    res_p = residual.data_ptr() if residual is not None else None
+    if lda == K and ldr == N:
+        hotpath.check(
+            lib.cc_gemm_bf16_ex(
+                x.data_ptr(), w_bf16.data_ptr(), out.data_ptr(), M, N, K,
+                bias_p, 1, act, res_p, stream,
+            )
         )
-    )
+    else:
+        hotpath.check(
+            lib.cc_gemm_bf16_strided(
+                x.data_ptr(), lda, w_bf16.data_ptr(), out.data_ptr(), M, N, K,
+                bias_p, 1, act, res_p, ldr, stream,
+            )
+        )
     return out
+
+
+def _row_stride(t: torch.Tensor) -> int | None:
+    """Row stride (elements) of a 2-D tensor the GEMM can read in place:
+    unit column stride and rows that do not overlap; None otherwise."""
+    rows, cols = t.shape
+    if t.stride(1) != 1 and cols != 1:
+        return None
+    if rows == 1:
+        return cols
+    return t.stride(0) if t.stride(0) >= cols else None
 
 
 class ClipVisionTowerAMD(torch.nn.Module):
@@ -70,7 +103,15 @@ class ClipVisionTowerAMD(torch.nn.Module):
     patch-embed GEMM's K = 3*patch^2 is zero-padded to the kernel's
     64-multiple requirement (588 -> 640 for L/14) — exact, the padded
     columns multiply zeros.
+
+    ``prune_last_layer`` (default True): the embedding reads only the CLS
+    row of the last encoder layer, so that layer computes Q, attention,
+    out-proj, LN2 and the MLP for the CLS rows only (_last_layer_cls).
+    False runs the full layer on every token — for A/B runs and parity
+    tests; it is also what head dims other than 64 get on the GPU.
     """
+
+    prune_last_layer = True
 
     def __init__(
         self,
@@ -207,7 +248,16 @@ class ClipVisionTowerAMD(torch.nn.Module):
             h = (h.float() + self.pos_emb.unsqueeze(0)).to(torch.bfloat16)
             h = self._ln(h, self.pre_ln_w, self.pre_ln_b)
         hd = cfg.hidden // self.heads
+        # pooling reads only the CLS row of the last layer's output, so
+        # that layer runs everything past K/V on the CLS rows alone
+        cls_only = (
+            self.prune_last_layer and cfg.has_cls
+            and (hd == 64 or not h.is_cuda)
+        )
         for i in range(self.layers):
+            if cls_only and i == self.layers - 1:
+                h = self._last_layer_cls(h, i, n, seq)
+                break
             res = h
             y = self._ln(h, getattr(self, f"ln1_w_{i}"), getattr(self, f"ln1_b_{i}"))
             qkv_flat = self._linear(
@@ -263,6 +313,62 @@ class ClipVisionTowerAMD(torch.nn.Module):
                 residual=res.reshape(n * seq, cfg.hidden),
             ).reshape(n, seq, cfg.hidden)
 
-        pooled = self._ln(h[:, 0], self.post_ln_w, self.post_ln_b)
+        cls_rows = h if cls_only else h[:, 0]
+        pooled = self._ln(cls_rows, self.post_ln_w, self.post_ln_b)
         emb = self._linear(pooled.to(torch.bfloat16), self.w_proj, None).float()
         return emb / torch.linalg.vector_norm(emb, dim=-1, keepdim=True)
+
+    def _last_layer_cls(
+        self, h: torch.Tensor, i: int, n: int, seq: int
+    ) -> torch.Tensor:
+        """Encoder layer ``i`` for the CLS rows only: (n, seq, H) -> (n, H).
+
+        Every token still feeds attention as a key and a value, so LN1 and
+        the K/V two thirds of the QKV projection run on all rows.  The Q
+        projection, the attention output, out-proj, LN2 and the MLP are
+        row-wise, so computing them for row 0 of each frame gives exactly
+        the rows the full layer would have produced there.  The CLS rows
+        of the LN1 output (A of the Q GEMM) and of ``h`` (residual of
+        out-proj) are read in place through row strides.
+        """
+        H = self.cfg.hidden
+        hd = H // self.heads
+        w_qkv = getattr(self, f"w_qkv_{i}")
+        b_qkv = getattr(self, f"b_qkv_{i}")
+        y = self._ln(h, getattr(self, f"ln1_w_{i}"), getattr(self, f"ln1_b_{i}"))
+        # rows ordered (q, k, v): contiguous slices, no weight copies
+        kv = self._linear(y.reshape(n * seq, H), w_qkv[H:], b_qkv[H:])
+        q = self._linear(y[:, 0], w_qkv[:H], b_qkv[:H])
+        if kv.is_cuda:
+            lib = hotpath.require_gpu()
+            attn = torch.empty((n, H), dtype=torch.bfloat16, device=kv.device)
+            stream = torch.cuda.current_stream(kv.device).cuda_stream
+            hotpath.check(
+                lib.cc_attn_cls(
+                    q.data_ptr(), kv.data_ptr(),
+                    kv.data_ptr() + H * kv.element_size(), 2 * H,
+                    attn.data_ptr(), n, seq, self.heads, H,
+                    ctypes.c_float(self.scale), stream,
+                )
+            )
+        else:
+            kvh = kv.reshape(n, seq, 2, self.heads, hd)
+            attn = torch.nn.functional.scaled_dot_product_attention(
+                q.reshape(n, 1, self.heads, hd).permute(0, 2, 1, 3),
+                kvh[:, :, 0].permute(0, 2, 1, 3),
+                kvh[:, :, 1].permute(0, 2, 1, 3),
+                scale=self.scale,
+            )
+            attn = attn.permute(0, 2, 1, 3).reshape(n, H)
+        h1 = self._linear(
+            attn, getattr(self, f"w_out_{i}"), getattr(self, f"b_out_{i}"),
+            residual=h[:, 0],
+        )
+        y = self._ln(h1, getattr(self, f"ln2_w_{i}"), getattr(self, f"ln2_b_{i}"))
+        y = self._linear(
+            y, getattr(self, f"w_fc1_{i}"), getattr(self, f"b_fc1_{i}"), act=1
+        )
+        return self._linear(
+            y, getattr(self, f"w_fc2_{i}"), getattr(self, f"b_fc2_{i}"),
+            residual=h1,
+        )

@@ -173,6 +173,18 @@ int cc_gemm_bf16_ex(const void* A, const void* B, void* C,
                     int64_t M, int64_t N, int64_t K,
                     const float* bias, int c_dtype, int act,
                     const void* residual, uint64_t stream);
+/* Row-strided form: A row i starts at A + i*lda, residual row i at
+ * residual + i*ldr (elements; C stays dense [M,N]).  Lets the last
+ * encoder layer of a CLS-pooled tower (the hidden_states[:, 0] pooling
+ * under models/clip.py:71) run its Q projection and out-proj on the CLS
+ * rows of a [frames*seq, hidden] tensor in place, with no gather copy.
+ * lda >= K, lda % 8 == 0 (16-byte direct-to-LDS loads), ldr >= N; ldr is
+ * ignored when residual is NULL.  Strided launches run the 128-tile
+ * body; lda == K and ldr == N behaves exactly as cc_gemm_bf16_ex. */
+int cc_gemm_bf16_strided(const void* A, int64_t lda, const void* B, void* C,
+                         int64_t M, int64_t N, int64_t K, const float* bias,
+                         int c_dtype, int act, const void* residual,
+                         int64_t ldr, uint64_t stream);
 
 /* ---- fused short-sequence attention (ViT encoder; replaces torch sdpa
  * + the qkv permute copies).  qkv = the fused-QKV GEMM output
@@ -191,6 +203,19 @@ int cc_attn_mid(const void* qkv, void* out, int64_t n_frames, int seq,
  * with online softmax — covers SigLIP-384/so400m-class towers. */
 int cc_attn_flash(const void* qkv, void* out, int64_t n_frames, int seq,
                   int heads, int hidden, float scale, uint64_t stream);
+
+/* CLS-query variant (head dim 64, any seq >= 1): attention for ONE query
+ * row per (frame, head) against all seq keys/values — the only row of the
+ * last encoder layer that hidden_states[:, 0] pooling reads (replaces the
+ * last layer's torch sdpa under models/clip.py:71).  q [n_frames, hidden]
+ * bf16; k and v point at the first key / value row of a buffer whose
+ * rows (n_frames*seq of them) are ldkv elements apart, e.g. the two
+ * halves of the K/V GEMM output [n_frames*seq, 2*hidden]; out
+ * [n_frames, hidden] bf16.  ldkv >= hidden, ldkv % 8 == 0, pointers
+ * 16-byte aligned. */
+int cc_attn_cls(const void* q, const void* k, const void* v, int64_t ldkv,
+                void* out, int64_t n_frames, int seq, int heads, int hidden,
+                float scale, uint64_t stream);
 
 /* ---- fused bf16 LayerNorm (replaces torch layer_norm in the ViT
  * forward; f32 stats/affine, H multiple of 256). */
