@@ -3,7 +3,8 @@
 // Replaces NVDEC via PyNvVideoCodec (/root/reference/cosmos_curate/
 // pipelines/video/utils/nvcodec_utils.py:199-313: NvVideoDecoder /
 // VideoBatchDecoder): a parser + decoder session per clip stream, AnnexB
-// packets in (from cc_demux_packet), NV12 surfaces in HBM out.
+// packets in (from cc_demux_packet), NV12 (8-bit) or P016 (10/12-bit)
+// surfaces in HBM out.
 //
 // This ROCm image ships no librocdecode.so, but the public rocDecode API
 // headers are present (rocprofiler-sdk/rocdecode/details/rocdecode.h,
@@ -19,7 +20,8 @@
 // Session shape (mirrors NvVideoDecoder):
 //   create  -> rocDecCreateVideoParser (decoder created lazily at the
 //              first sequence callback, when the SPS geometry is known;
-//              format changes go through rocDecReconfigureDecoder)
+//              geometry changes go through rocDecReconfigureDecoder, a
+//              bit-depth change recreates the decoder: NV12 <-> P016)
 //   submit  -> rocDecParseVideoData (one AnnexB access unit per call;
 //              NULL packet = end of stream flush)
 //   map     -> drain the display queue; rocDecGetVideoFrame maps each
@@ -108,6 +110,8 @@ struct cc_decode {
   RocdecVideoParser parser = nullptr;
   rocDecDecoderHandle decoder = nullptr;
   RocdecVideoFormat format = {};        // from the last sequence callback
+                                        // (bit depth, matrix, range too)
+  bool have_format = false;             // a sequence callback has succeeded
   uint32_t surfaces = 0;                // decode surfaces the decoder holds
   std::deque<RocdecParserDispInfo> display_q;  // display-order, undrained
   std::vector<int> mapped;              // mapped pic indices (recycle list)
@@ -125,11 +129,35 @@ int seq_cb(void* user, RocdecVideoFormat* fmt) {
   auto* s = (cc_decode*)user;
   const uint32_t want_surfaces =
       fmt->min_num_decode_surfaces > 8 ? fmt->min_num_decode_surfaces : 8;
+  // 8-bit 4:2:0 -> NV12, 10/12-bit -> P016 (u16 samples, MSB-aligned): the
+  // two layouts cc_yuv420sp_to_rgb* consume.  Anything else stays loud.
+  const int minus8 = fmt->bit_depth_luma_minus8;
+  if (minus8 != 0 && minus8 != 2 && minus8 != 4) {
+    s->cb_error = cc::set_error(
+        CC_ERR_UNSUPPORTED, "unsupported bit depth %d (8, 10 and 12 map to "
+        "NV12/P016 surfaces)", 8 + minus8);
+    return 0;
+  }
+  if (s->decoder && minus8 != s->format.bit_depth_luma_minus8) {
+    // bit-depth change mid-stream: the surface format (NV12 <-> P016) is
+    // fixed at decoder creation, so reconfiguring in place would keep the
+    // wrong one.  Recreate the decoder — only possible while none of the
+    // old decoder's pictures is queued or mapped.
+    if (!s->display_q.empty() || !s->mapped.empty()) {
+      s->cb_error = cc::set_error(
+          CC_ERR_UNSUPPORTED, "bit depth changed %d -> %d with %zu queued and "
+          "%zu mapped pictures of the old surface format outstanding",
+          8 + s->format.bit_depth_luma_minus8, 8 + minus8,
+          s->display_q.size(), s->mapped.size());
+      return 0;
+    }
+    s->api->DestroyDecoder(s->decoder);
+    s->decoder = nullptr;
+  }
   if (s->decoder) {
     if (fmt->coded_width == s->format.coded_width &&
         fmt->coded_height == s->format.coded_height &&
-        fmt->codec == s->format.codec &&
-        fmt->bit_depth_luma_minus8 == s->format.bit_depth_luma_minus8) {
+        fmt->codec == s->format.codec) {
       s->format = *fmt;
       return (int)s->surfaces;  // no geometry change
     }
@@ -165,16 +193,8 @@ int seq_cb(void* user, RocdecVideoFormat* fmt) {
   ci.bit_depth_minus_8 = fmt->bit_depth_luma_minus8;
   ci.num_decode_surfaces = want_surfaces;
   ci.num_output_surfaces = 4;
-  // 8-bit 4:2:0 -> NV12 (the downstream kernels' input layout); 10/12-bit
-  // would map P016 — rejected below until a kernel consumes it.
-  ci.output_format = rocDecVideoSurfaceFormat_NV12;
-  if (fmt->bit_depth_luma_minus8 != 0) {
-    s->cb_error = cc::set_error(
-        CC_ERR_UNSUPPORTED, "high-bit-depth stream (bit depth %d): no "
-        "NV12 surface; P016 path not wired",
-        8 + fmt->bit_depth_luma_minus8);
-    return 0;
-  }
+  ci.output_format = minus8 ? rocDecVideoSurfaceFormat_P016
+                            : rocDecVideoSurfaceFormat_NV12;
   ci.display_rect.left = (int16_t)fmt->display_area.left;
   ci.display_rect.top = (int16_t)fmt->display_area.top;
   ci.display_rect.right = (int16_t)fmt->display_area.right;
@@ -189,6 +209,7 @@ int seq_cb(void* user, RocdecVideoFormat* fmt) {
     return 0;
   }
   s->format = *fmt;
+  s->have_format = true;
   s->surfaces = want_surfaces;
   return (int)want_surfaces;
 }
@@ -303,10 +324,13 @@ int cc_decode_map_frames(cc_decode* s, cc_nv12_frame* out, size_t cap,
     cc_nv12_frame* f = &out[(*n)++];
     // apply the display crop origin (usually 0,0; e.g. 1920x1088 coded
     // with display_area {0,0,1920,1080}): callers see display pixels.
-    const int left = s->format.display_area.left & ~1;  // NV12: even x
+    // rocDecGetVideoFrame takes ONE pitch pointer: pitch[0] is the row
+    // stride in bytes of both planes (NV12 and P016 share it).
+    const int left = s->format.display_area.left & ~1;  // 4:2:0: even x
     const int top = s->format.display_area.top & ~1;
-    f->y = (uint8_t*)planes[0] + (size_t)top * pitch[0] + left;
-    f->uv = (uint8_t*)planes[1] + (size_t)(top / 2) * pitch[1] + left;
+    const size_t bps = s->format.bit_depth_luma_minus8 ? 2 : 1;
+    f->y = (uint8_t*)planes[0] + (size_t)top * pitch[0] + left * bps;
+    f->uv = (uint8_t*)planes[1] + (size_t)(top / 2) * pitch[0] + left * bps;
     f->pitch = pitch[0];
     f->pts = (int64_t)disp.pts;
     f->width = (uint32_t)(s->format.display_area.right -
@@ -317,6 +341,21 @@ int cc_decode_map_frames(cc_decode* s, cc_nv12_frame* out, size_t cap,
     if (!f->height) f->height = s->format.coded_height;
     s->mapped.push_back(disp.picture_index);
   }
+  return CC_OK;
+}
+
+int cc_decode_stream_format(const cc_decode* s, cc_stream_format* out) {
+  if (!s || !out) return cc::set_error(CC_ERR_INVALID, "bad args");
+  if (!s->have_format)
+    return cc::set_error(CC_ERR_INVALID,
+                         "stream format unknown before the first sequence "
+                         "header");
+  out->bit_depth = 8 + s->format.bit_depth_luma_minus8;
+  out->chroma_format = (int32_t)s->format.chroma_format;
+  out->matrix_coefficients =
+      s->format.video_signal_description.matrix_coefficients;
+  out->full_range = s->format.video_signal_description.video_full_range_flag;
+  out->bytes_per_sample = s->format.bit_depth_luma_minus8 ? 2 : 1;
   return CC_OK;
 }
 

@@ -140,6 +140,211 @@ __global__ void k_nv12_to_rgb_resize(const unsigned char* __restrict__ y,
   }
 }
 
+// ---------------- 8/10/12-bit 4:2:0 semi-planar -> RGB ----------------
+// NV12 (u8 samples) and P016 (u16 samples, MSB-aligned) with a selectable
+// matrix and range.  Per sample, in f32 and in this order (the contract
+// tests/yuv_ref.py restates):
+//   s = sample >> (16 - depth)            (depth 8: s = sample)
+//   x = float(s) * 2^-(depth-8)           (exact)
+//   yf = x_Y - yoff, u = x_U - 128, v = x_V - 128
+//   fy = CY*yf; R = fy + CVR*v; G = fy + CVG*v + CUG*u; B = fy + CUB*u
+//   round_u8 each.
+struct YuvCoef {
+  float yoff, cy, cvr, cvg, cug, cub;
+};
+
+// [matrix 0=BT.601 1=BT.709 2=BT.2020-NCL][0 = limited range, 1..3 = full
+// range at depth 8/10/12].  Limited: yoff 16, CY 255/219, chroma scale
+// sc 255/224; full: yoff 0, CY = sc = 255*2^(d-8)/(2^d-1);
+// CVR 2(1-Kr)sc, CVG -2Kr(1-Kr)/Kg*sc, CUG -2Kb(1-Kb)/Kg*sc, CUB 2(1-Kb)sc.
+// Every row is the double-precision formula rounded to f32, EXCEPT BT.601
+// limited, which repeats yuv_to_rgb_f's literals verbatim (its CVR/CVG sit
+// one ulp off the formula; the 8-bit kernels and oracle/color.py are
+// pinned to them).
+const YuvCoef kYuvCoef[3][4] = {
+    {{16.0f, 1.1643835f, 1.5960267f, -0.8129676f, -0.3917623f, 2.0172321f},
+     {0.0f, 1.0f, 1.40199995f, -0.714136302f, -0.344136298f, 1.77199996f},
+     {0.0f, 0.997067451f, 1.39788854f, -0.712042034f, -0.343127102f,
+      1.7668035f},
+     {0.0f, 0.996336997f, 1.39686441f, -0.711520374f, -0.342875719f,
+      1.76550913f}},
+    {{16.0f, 1.16438353f, 1.79274106f, -0.532909334f, -0.21324861f,
+      2.11240172f},
+     {0.0f, 1.0f, 1.57480001f, -0.46812427f, -0.187324271f, 1.8556f},
+     {0.0f, 0.997067451f, 1.57018185f, -0.466751486f, -0.186774939f,
+      1.85015833f},
+     {0.0f, 0.996336997f, 1.56903148f, -0.466409534f, -0.186638102f,
+      1.84880292f}},
+    {{16.0f, 1.16438353f, 1.6786741f, -0.650424302f, -0.187326103f,
+      2.14177227f},
+     {0.0f, 1.0f, 1.47459996f, -0.571353137f, -0.164553121f, 1.88139999f},
+     {0.0f, 0.997067451f, 1.47027564f, -0.569677591f, -0.164070562f,
+      1.87588274f},
+     {0.0f, 0.996336997f, 1.46919858f, -0.56926024f, -0.163950369f,
+      1.87450838f}},
+};
+
+__device__ __forceinline__ uchar3 yuv_to_rgb_u8(unsigned sy, unsigned su,
+                                                unsigned sv, int shift,
+                                                float scale,
+                                                const YuvCoef& k) {
+  float yf = (float)(sy >> shift) * scale - k.yoff;
+  float u = (float)(su >> shift) * scale - 128.0f;
+  float v = (float)(sv >> shift) * scale - 128.0f;
+  float fy = k.cy * yf;
+  return {round_u8(fy + k.cvr * v), round_u8(fy + k.cvg * v + k.cug * u),
+          round_u8(fy + k.cub * u)};
+}
+
+// one pixel (full-res coords); T = sample type, pitch in bytes
+template <typename T>
+__device__ __forceinline__ uchar3 yuv420sp_px(
+    const unsigned char* __restrict__ y, const unsigned char* __restrict__ uv,
+    size_t pitch, int yy, int xx, int shift, float scale, const YuvCoef& k) {
+  const T* yr = (const T*)(y + (size_t)yy * pitch);
+  const T* uvr = (const T*)(uv + (size_t)(yy >> 1) * pitch);
+  int cx = xx & ~1;
+  return yuv_to_rgb_u8(yr[xx], uvr[cx], uvr[cx + 1], shift, scale, k);
+}
+
+// Scalar path: one thread per pixel over columns [x_start, w) of every
+// row — the w % 8 row tails, or whole frames (x_start = 0) whose planes
+// are not 16-byte aligned.
+template <typename T>
+__global__ void k_yuv420sp_to_rgb_px(const unsigned char* __restrict__ y,
+                                     const unsigned char* __restrict__ uv,
+                                     int n, int h, int w, int x_start,
+                                     size_t pitch, int shift, float scale,
+                                     YuvCoef k,
+                                     unsigned char* __restrict__ out) {
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int cw = w - x_start;
+  long total = (long)n * h * cw;
+  if (idx >= total) return;
+  int xx = x_start + (int)(idx % cw);
+  long t = idx / cw;
+  int yy = t % h;
+  int f = t / h;
+  uchar3 rgb = yuv420sp_px<T>(y + (size_t)f * pitch * h,
+                              uv + (size_t)f * pitch * (h / 2), pitch, yy, xx,
+                              shift, scale, k);
+  unsigned char* o = out + (((size_t)f * h + yy) * w + xx) * 3;
+  o[0] = rgb.x;
+  o[1] = rgb.y;
+  o[2] = rgb.z;
+}
+
+struct __attribute__((packed)) rgb8_run {
+  unsigned int d[6];
+};
+
+// Vector path: one lane per run of 8 pixels of one row.  One load of 8 Y
+// samples and one of the 4 chroma pairs they share (16 B each at 16 bit,
+// 8 B at 8 bit; planes and pitch 16-byte aligned, checked by the
+// launcher), 24 contiguous output bytes stored as dwords.  Bandwidth-
+// bound: 3 B/px in at 16 bit, 3 B/px out.  Sample and byte positions are
+// compile-time constants after unrolling, so nothing is indexed at run
+// time and nothing spills.
+template <typename T>
+__global__ void k_yuv420sp_to_rgb_v8(const unsigned char* __restrict__ y,
+                                     const unsigned char* __restrict__ uv,
+                                     int n, int h, int w, size_t pitch,
+                                     int shift, float scale, YuvCoef k,
+                                     unsigned char* __restrict__ out) {
+  constexpr int BITS = 8 * (int)sizeof(T);
+  constexpr int PER = 32 / BITS;  // samples per dword
+  constexpr unsigned MASK = (1u << BITS) - 1u;
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int runs = w / 8;
+  long total = (long)n * h * runs;
+  if (idx >= total) return;
+  int x0 = (int)(idx % runs) * 8;
+  long t = idx / runs;
+  int yy = t % h;
+  int f = t / h;
+  const unsigned char* yp =
+      y + (size_t)f * pitch * h + (size_t)yy * pitch + (size_t)x0 * sizeof(T);
+  const unsigned char* uvp = uv + (size_t)f * pitch * (h / 2) +
+                             (size_t)(yy >> 1) * pitch +
+                             (size_t)x0 * sizeof(T);
+  unsigned int yw[4], cw[4];
+  if constexpr (sizeof(T) == 2) {
+    *(uint4*)yw = *(const uint4*)yp;
+    *(uint4*)cw = *(const uint4*)uvp;
+  } else {
+    *(uint2*)yw = *(const uint2*)yp;
+    *(uint2*)cw = *(const uint2*)uvp;
+  }
+  unsigned int o[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const int ju = j & ~1, jv = ju + 1;
+    uchar3 rgb = yuv_to_rgb_u8((yw[j / PER] >> (BITS * (j % PER))) & MASK,
+                               (cw[ju / PER] >> (BITS * (ju % PER))) & MASK,
+                               (cw[jv / PER] >> (BITS * (jv % PER))) & MASK,
+                               shift, scale, k);
+    o[(3 * j) >> 2] |= (unsigned)rgb.x << (8 * ((3 * j) & 3));
+    o[(3 * j + 1) >> 2] |= (unsigned)rgb.y << (8 * ((3 * j + 1) & 3));
+    o[(3 * j + 2) >> 2] |= (unsigned)rgb.z << (8 * ((3 * j + 2) & 3));
+  }
+  unsigned char* op = out + (((size_t)f * h + yy) * w + x0) * 3;
+  if (((size_t)op & 7) == 0) {
+    // dense NHWC rows with w % 4 == 0 off an aligned base: always here
+    uint2* o8 = (uint2*)op;
+    o8[0] = make_uint2(o[0], o[1]);
+    o8[1] = make_uint2(o[2], o[3]);
+    o8[2] = make_uint2(o[4], o[5]);
+  } else {
+    // unaligned dword stores (e.g. w = 66, odd rows)
+    *(rgb8_run*)op = rgb8_run{{o[0], o[1], o[2], o[3], o[4], o[5]}};
+  }
+}
+
+// Fused convert + bilinear resize, same definition as
+// k_nv12_to_rgb_resize: every tap converted and rounded to u8 first.
+template <typename T>
+__global__ void k_yuv420sp_to_rgb_resize(
+    const unsigned char* __restrict__ y, const unsigned char* __restrict__ uv,
+    int n, int sh, int sw, size_t pitch, int shift, float scale, YuvCoef k,
+    unsigned char* __restrict__ out, int dh, int dw) {
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long total = (long)n * dh * dw;
+  if (idx >= total) return;
+  int dx = idx % dw;
+  long t = idx / dw;
+  int dy = t % dh;
+  int f = t / dh;
+  const unsigned char* yp = y + (size_t)f * pitch * sh;
+  const unsigned char* uvp = uv + (size_t)f * pitch * (sh / 2);
+
+  float syf = src_coord(dy, dh, sh);
+  float sxf = src_coord(dx, dw, sw);
+  int y0 = (int)fminf(fmaxf(floorf(syf), 0.0f), (float)(sh - 1));
+  int x0 = (int)fminf(fmaxf(floorf(sxf), 0.0f), (float)(sw - 1));
+  int y1 = min(y0 + 1, sh - 1);
+  int x1 = min(x0 + 1, sw - 1);
+  float wy = fminf(fmaxf(syf - (float)y0, 0.0f), 1.0f);
+  float wx = fminf(fmaxf(sxf - (float)x0, 0.0f), 1.0f);
+
+  uchar3 p00 = yuv420sp_px<T>(yp, uvp, pitch, y0, x0, shift, scale, k);
+  uchar3 p01 = yuv420sp_px<T>(yp, uvp, pitch, y0, x1, shift, scale, k);
+  uchar3 p10 = yuv420sp_px<T>(yp, uvp, pitch, y1, x0, shift, scale, k);
+  uchar3 p11 = yuv420sp_px<T>(yp, uvp, pitch, y1, x1, shift, scale, k);
+
+  unsigned char* o = out + ((size_t)idx) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    float v00 = (float)(c == 0 ? p00.x : c == 1 ? p00.y : p00.z);
+    float v01 = (float)(c == 0 ? p01.x : c == 1 ? p01.y : p01.z);
+    float v10 = (float)(c == 0 ? p10.x : c == 1 ? p10.y : p10.z);
+    float v11 = (float)(c == 0 ? p11.x : c == 1 ? p11.y : p11.z);
+    float top = v00 * (1.0f - wx) + v01 * wx;
+    float bot = v10 * (1.0f - wx) + v11 * wx;
+    float val = top * (1.0f - wy) + bot * wy;
+    o[c] = round_u8(val);
+  }
+}
+
 // ---------------- u8 NHWC bilinear resize ----------------
 __global__ void k_resize_bilinear_u8(const unsigned char* __restrict__ in,
                                      int n, int sh, int sw,
@@ -567,6 +772,113 @@ int cc_nv12_to_rgb_resize(const void* y, const void* uv, int n, int src_h,
   CC_LAUNCH("nv12_to_rgb_resize", grid, block, stream, k_nv12_to_rgb_resize,
             (const unsigned char*)y, (const unsigned char*)uv, n, src_h, src_w,
             pitch, (unsigned char*)out_rgb, out_h, out_w);
+  return CC_OK;
+}
+
+// argument checks shared by the two cc_yuv420sp_* launchers (all before
+// any launch)
+static int yuv420sp_check(const void* y, const void* uv, const void* out,
+                          int n, int h, int w, size_t pitch, int bit_depth,
+                          int matrix, int full_range) {
+  if (!y || !uv || !out)
+    return cc::set_error(CC_ERR_INVALID, "yuv420sp: null pointer");
+  if (n <= 0 || h <= 0 || w <= 0)
+    return cc::set_error(CC_ERR_INVALID, "yuv420sp: non-positive size n=%d "
+                         "h=%d w=%d", n, h, w);
+  if ((h & 1) || (w & 1))
+    return cc::set_error(CC_ERR_INVALID,
+                         "yuv420sp: 4:2:0 needs even dims (got %dx%d)", w, h);
+  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12)
+    return cc::set_error(CC_ERR_INVALID,
+                         "yuv420sp: bit_depth must be 8, 10 or 12 (got %d)",
+                         bit_depth);
+  if (matrix < 0 || matrix > 2)
+    return cc::set_error(CC_ERR_INVALID, "yuv420sp: matrix must be 0 (bt601), "
+                         "1 (bt709) or 2 (bt2020) (got %d)", matrix);
+  if (full_range != 0 && full_range != 1)
+    return cc::set_error(CC_ERR_INVALID,
+                         "yuv420sp: full_range must be 0 or 1 (got %d)",
+                         full_range);
+  const size_t bps = bit_depth == 8 ? 1 : 2;
+  if (pitch < (size_t)w * bps)
+    return cc::set_error(CC_ERR_INVALID, "yuv420sp: pitch %zu < row bytes %zu",
+                         pitch, (size_t)w * bps);
+  if (bps == 2 && ((pitch | (size_t)y | (size_t)uv) & 1))
+    return cc::set_error(CC_ERR_INVALID, "yuv420sp: 16-bit planes need an "
+                         "even pitch and 2-byte-aligned pointers");
+  return CC_OK;
+}
+
+int cc_yuv420sp_to_rgb(const void* y, const void* uv, int n, int h, int w,
+                       size_t pitch_bytes, int bit_depth, int matrix,
+                       int full_range, void* out_rgb, uint64_t stream) {
+  int rc = yuv420sp_check(y, uv, out_rgb, n, h, w, pitch_bytes, bit_depth,
+                          matrix, full_range);
+  if (rc != CC_OK) return rc;
+  const YuvCoef k = kYuvCoef[matrix][full_range ? 1 + (bit_depth - 8) / 2 : 0];
+  const int shift = bit_depth == 8 ? 0 : 16 - bit_depth;
+  const float scale = 1.0f / (float)(1 << (bit_depth - 8));
+  const unsigned char* yp = (const unsigned char*)y;
+  const unsigned char* uvp = (const unsigned char*)uv;
+  unsigned char* op = (unsigned char*)out_rgb;
+  // 16-byte-aligned planes and pitch: 8-pixel runs go through the vector
+  // kernel and only the w % 8 row tails through the scalar one
+  const bool aligned = (((size_t)y | (size_t)uv | pitch_bytes) & 15) == 0;
+  const int x_vec = aligned ? (w / 8) * 8 : 0;
+  dim3 block(256);
+  if (x_vec > 0) {
+    long runs = (long)n * h * (w / 8);
+    dim3 grid((unsigned)((runs + 255) / 256));
+    if (bit_depth == 8)
+      CC_LAUNCH("yuv420sp_to_rgb", grid, block, stream,
+                k_yuv420sp_to_rgb_v8<uint8_t>, yp, uvp, n, h, w, pitch_bytes,
+                shift, scale, k, op);
+    else
+      CC_LAUNCH("yuv420sp_to_rgb", grid, block, stream,
+                k_yuv420sp_to_rgb_v8<uint16_t>, yp, uvp, n, h, w, pitch_bytes,
+                shift, scale, k, op);
+  }
+  if (x_vec < w) {
+    long total = (long)n * h * (w - x_vec);
+    dim3 grid((unsigned)((total + 255) / 256));
+    if (bit_depth == 8)
+      CC_LAUNCH("yuv420sp_to_rgb", grid, block, stream,
+                k_yuv420sp_to_rgb_px<uint8_t>, yp, uvp, n, h, w, x_vec,
+                pitch_bytes, shift, scale, k, op);
+    else
+      CC_LAUNCH("yuv420sp_to_rgb", grid, block, stream,
+                k_yuv420sp_to_rgb_px<uint16_t>, yp, uvp, n, h, w, x_vec,
+                pitch_bytes, shift, scale, k, op);
+  }
+  return CC_OK;
+}
+
+int cc_yuv420sp_to_rgb_resize(const void* y, const void* uv, int n, int src_h,
+                              int src_w, size_t pitch_bytes, int bit_depth,
+                              int matrix, int full_range, void* out_rgb,
+                              int out_h, int out_w, uint64_t stream) {
+  int rc = yuv420sp_check(y, uv, out_rgb, n, src_h, src_w, pitch_bytes,
+                          bit_depth, matrix, full_range);
+  if (rc != CC_OK) return rc;
+  if (out_h <= 0 || out_w <= 0)
+    return cc::set_error(CC_ERR_INVALID,
+                         "yuv420sp: non-positive output size %dx%d", out_w,
+                         out_h);
+  const YuvCoef k = kYuvCoef[matrix][full_range ? 1 + (bit_depth - 8) / 2 : 0];
+  const int shift = bit_depth == 8 ? 0 : 16 - bit_depth;
+  const float scale = 1.0f / (float)(1 << (bit_depth - 8));
+  long total = (long)n * out_h * out_w;
+  dim3 block(256), grid((unsigned)((total + 255) / 256));
+  if (bit_depth == 8)
+    CC_LAUNCH("yuv420sp_to_rgb_resize", grid, block, stream,
+              k_yuv420sp_to_rgb_resize<uint8_t>, (const unsigned char*)y,
+              (const unsigned char*)uv, n, src_h, src_w, pitch_bytes, shift,
+              scale, k, (unsigned char*)out_rgb, out_h, out_w);
+  else
+    CC_LAUNCH("yuv420sp_to_rgb_resize", grid, block, stream,
+              k_yuv420sp_to_rgb_resize<uint16_t>, (const unsigned char*)y,
+              (const unsigned char*)uv, n, src_h, src_w, pitch_bytes, shift,
+              scale, k, (unsigned char*)out_rgb, out_h, out_w);
   return CC_OK;
 }
 

@@ -48,6 +48,7 @@ def _declare(lib: ctypes.CDLL) -> None:
         c.c_void_p, c.c_char_p, c.c_size_t, c.c_int64]
     lib.cc_decode_map_frames.argtypes = [
         c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]
+    lib.cc_decode_stream_format.argtypes = [c.c_void_p, c.c_void_p]
     lib.cc_decode_recycle.argtypes = [c.c_void_p]
     lib.cc_decode_destroy.argtypes = [c.c_void_p]
 
@@ -63,6 +64,12 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.cc_nv12_to_rgb_resize.argtypes = [
         c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_size_t,
         c.c_void_p, c.c_int, c.c_int, c.c_uint64]
+    lib.cc_yuv420sp_to_rgb.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_size_t,
+        c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_uint64]
+    lib.cc_yuv420sp_to_rgb_resize.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_size_t,
+        c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_int, c.c_int, c.c_uint64]
     lib.cc_resize_bilinear_u8.argtypes = [
         c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_int, c.c_int,
         c.c_uint64]
@@ -147,6 +154,27 @@ def check(rc: int) -> None:
         raise RuntimeError(f"cc error {rc}: {lib.cc_last_error().decode()}")
 
 
+def yuv_to_rgb_resize(
+    y: int, uv: int, n: int, src_h: int, src_w: int, pitch_bytes: int,
+    out_rgb: int, out_h: int, out_w: int, stream: int, *,
+    bit_depth: int = 8, matrix: int = 0, full_range: bool = False,
+) -> None:
+    """Fused 4:2:0 semi-planar -> RGB + bilinear resize on device pointers.
+
+    8-bit BT.601 limited range stays on cc_nv12_to_rgb_resize (the path and
+    the bits every 8-bit consumer has always had); every other combination
+    runs cc_yuv420sp_to_rgb_resize.  No fallback: a failing call raises.
+    """
+    lib = load()
+    if bit_depth == 8 and matrix == 0 and not full_range:
+        check(lib.cc_nv12_to_rgb_resize(
+            y, uv, n, src_h, src_w, pitch_bytes, out_rgb, out_h, out_w, stream))
+    else:
+        check(lib.cc_yuv420sp_to_rgb_resize(
+            y, uv, n, src_h, src_w, pitch_bytes, bit_depth, matrix,
+            int(bool(full_range)), out_rgb, out_h, out_w, stream))
+
+
 class VideoInfo(ctypes.Structure):
     _fields_ = [
         ("width", ctypes.c_uint32),
@@ -161,7 +189,8 @@ class VideoInfo(ctypes.Structure):
 
 
 class Nv12Frame(ctypes.Structure):
-    """cc_nv12_frame: a mapped VCN NV12 surface (device pointers)."""
+    """cc_nv12_frame: a mapped VCN NV12 or P016 surface (device pointers;
+    pitch in bytes)."""
 
     _fields_ = [
         ("y", ctypes.c_void_p),
@@ -170,6 +199,18 @@ class Nv12Frame(ctypes.Structure):
         ("pts", ctypes.c_int64),
         ("width", ctypes.c_uint32),
         ("height", ctypes.c_uint32),
+    ]
+
+
+class StreamFormat(ctypes.Structure):
+    """cc_stream_format: what the stream's sequence header signalled."""
+
+    _fields_ = [
+        ("bit_depth", ctypes.c_int32),
+        ("chroma_format", ctypes.c_int32),
+        ("matrix_coefficients", ctypes.c_int32),
+        ("full_range", ctypes.c_int32),
+        ("bytes_per_sample", ctypes.c_int32),
     ]
 
 
@@ -202,6 +243,13 @@ class DecodeSession:
         check(self._lib.cc_decode_map_frames(
             self._h, ctypes.byref(arr), cap, ctypes.byref(n)))
         return [arr[i] for i in range(n.value)]
+
+    def stream_format(self) -> StreamFormat:
+        """Bit depth, chroma format and colour signalling of the stream;
+        raises before the first sequence header has been parsed."""
+        fmt = StreamFormat()
+        check(self._lib.cc_decode_stream_format(self._h, ctypes.byref(fmt)))
+        return fmt
 
     def recycle(self) -> None:
         check(self._lib.cc_decode_recycle(self._h))

@@ -222,7 +222,7 @@ def chunk_tasks(
 
 
 def _slice_raw_clip(raw: bytes | np.ndarray, span: tuple[float, float]) -> np.ndarray:
-    """Frame-exact raw-NV12 span slice: frames with i/fps in [start, end).
+    """Frame-exact raw NV12/P016 span slice: frames with i/fps in [start, end).
 
     Zero-copy when the span covers the whole source; otherwise one
     header+body concatenation (frames are contiguous in the payload), no
@@ -238,9 +238,11 @@ def _slice_raw_clip(raw: bytes | np.ndarray, span: tuple[float, float]) -> np.nd
     buf = np.frombuffer(raw, dtype=np.uint8)
     if first == 0 and last == n:
         return buf  # span covers the whole source: zero-copy payload
-    fsz = h * w + (h // 2) * w
+    fsz = raw_backend.frame_nbytes(raw)
     num = int(round(fps))
-    hdr = raw_backend.pack_header(last - first, h, w, num, 1)
+    depth, matrix, full_range, _ = raw_backend.parse_format(raw)
+    hdr = raw_backend.pack_header(last - first, h, w, num, 1, bit_depth=depth,
+                                  matrix=matrix, full_range=full_range)
     body = buf[raw_backend.HEADER_SIZE + first * fsz:
                raw_backend.HEADER_SIZE + last * fsz]
     return np.concatenate([np.frombuffer(hdr, dtype=np.uint8), body])

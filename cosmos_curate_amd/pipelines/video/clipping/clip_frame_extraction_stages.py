@@ -11,7 +11,9 @@ MI355X path:
     demux (cc_demux_* / null-raw header)             [host]
     sample_closest on PTS                            [host, §8 row a2]
     NV12 surfaces -> HBM (rocDecode | raw upload)    [device]
-    fused NV12->RGB + bilinear resize kernel         [device, §2b rows 3-5]
+    fused YUV->RGB + bilinear resize kernel          [device, §2b rows 3-5]
+      (8-bit BT.601: cc_nv12_to_rgb_resize; 10/12-bit P016 or another
+       colour standard: cc_yuv420sp_to_rgb_resize)
     duplicate-count broadcast (cc_gather_frames_u8)  [device]
 
 Output frames live on DEVICE as torch uint8 NHWC tensors keyed by
@@ -51,8 +53,22 @@ from cosmos_curate_amd.pipelines.video.utils.decoder_utils import (
 )
 
 
+# color_standard -> conversion-kernel matrix code (cc_yuv420sp_to_rgb*)
+_FORCED_MATRIX = {"bt601": 0, "bt709": 1, "bt2020": 2}
+# H.273 matrix_coefficients -> kernel matrix code; everything else
+# (unspecified = 2 included) converts as BT.601
+_H273_MATRIX = {1: 1, 5: 0, 6: 0, 9: 2}
+
+
 class ClipFrameExtractionStage(CuratorStage):
-    """clip_frame_extraction_stages.py:43-192, GPU-native inside."""
+    """clip_frame_extraction_stages.py:43-192, GPU-native inside.
+
+    ``color_standard`` picks the YUV->RGB matrix: ``"bt601"`` (default;
+    BT.601 limited range for every input, what the reference's fixed
+    cvcuda conversion does), ``"bt709"`` / ``"bt2020"`` (that matrix,
+    limited range), or ``"stream"`` (matrix and range the clip signals:
+    the decoder's sequence header, or the raw payload's header).
+    """
 
     def __init__(
         self,
@@ -66,7 +82,12 @@ class ClipFrameExtractionStage(CuratorStage):
         verbose: bool = False,
         log_stats: bool = False,
         to_host: bool = False,
+        color_standard: str = "bt601",
     ) -> None:
+        if color_standard != "stream" and color_standard not in _FORCED_MATRIX:
+            msg = (f"color_standard must be one of bt601, bt709, bt2020, "
+                   f"stream; got {color_standard!r}")
+            raise ValueError(msg)
         if target_fps is None:
             target_fps = [2]
         if target_res is None:
@@ -79,6 +100,7 @@ class ClipFrameExtractionStage(CuratorStage):
         self._verbose = verbose
         self._log_stats = log_stats
         self._to_host = to_host
+        self._color_standard = color_standard
 
     @property
     def resources(self) -> CuratorStageResource:
@@ -92,6 +114,13 @@ class ClipFrameExtractionStage(CuratorStage):
 
         return reduce(lcm, fps)
 
+    def _color(self, matrix: int, full_range: bool) -> tuple[int, bool]:
+        """(kernel matrix code, full_range) to convert with, given what the
+        clip signals (already as a kernel matrix code)."""
+        if self._color_standard == "stream":
+            return matrix, full_range
+        return _FORCED_MATRIX[self._color_standard], False
+
     # ---- device pipeline -------------------------------------------------
     def _extract_clip_frames(
         self, data: bytes, sample_rate_fps: float
@@ -101,6 +130,8 @@ class ClipFrameExtractionStage(CuratorStage):
         if raw_backend.is_raw_nv12(data):
             ts = raw_backend.timestamps(data)
             n_frames, src_h, src_w, _ = raw_backend.parse_header(data)
+            depth, sig_matrix, sig_full, bps = raw_backend.parse_format(data)
+            matrix, full_range = self._color(sig_matrix, sig_full)
         else:
             rc = lib.cc_rocdecode_available()
             if rc != 0:
@@ -112,20 +143,20 @@ class ClipFrameExtractionStage(CuratorStage):
         if th <= 0 or tw <= 0:
             th, tw = src_h, src_w
 
-        # host gather of the unique selected NV12 frames, then one h2d
+        # host gather of the unique selected NV12/P016 frames, then one h2d
         ys, uvs = raw_backend.frame_planes(data, idx)
         dev = torch.device("cuda")
-        y_dev = torch.from_numpy(ys).to(dev, non_blocking=True)
-        uv_dev = torch.from_numpy(uvs).to(dev, non_blocking=True)
+        # uploaded as bytes: P016 planes are u16, the kernels take pointers
+        y_dev = torch.from_numpy(ys.view(np.uint8)).to(dev, non_blocking=True)
+        uv_dev = torch.from_numpy(uvs.view(np.uint8)).to(dev, non_blocking=True)
         stream = torch.cuda.current_stream(dev).cuda_stream
 
         n_sel = len(idx)
         rgb = torch.empty((n_sel, th, tw, 3), dtype=torch.uint8, device=dev)
-        hotpath.check(
-            lib.cc_nv12_to_rgb_resize(
-                y_dev.data_ptr(), uv_dev.data_ptr(), n_sel, src_h, src_w, src_w,
-                rgb.data_ptr(), th, tw, stream,
-            )
+        hotpath.yuv_to_rgb_resize(
+            y_dev.data_ptr(), uv_dev.data_ptr(), n_sel, src_h, src_w,
+            src_w * bps, rgb.data_ptr(), th, tw, stream,
+            bit_depth=depth, matrix=matrix, full_range=full_range,
         )
         total = int(counts.sum())
         if total == n_sel and np.all(counts == 1):
@@ -189,6 +220,14 @@ class ClipFrameExtractionStage(CuratorStage):
                     frames = sess.map_frames()
                     if not frames:
                         return
+                    # one query per batch of mapped frames, not per stream:
+                    # a mid-stream bit-depth change recreates the decoder
+                    # (NV12 <-> P016) only between batches, so every frame
+                    # of this batch has this format
+                    fmt = sess.stream_format()
+                    matrix, full_range = self._color(
+                        _H273_MATRIX.get(int(fmt.matrix_coefficients), 0),
+                        bool(fmt.full_range))
                     launched = False
                     for f in frames:
                         slot = slot_by_tick.get(int(f.pts))
@@ -206,10 +245,12 @@ class ClipFrameExtractionStage(CuratorStage):
                                    f"{tuple(rgb.shape[1:3])} -> {(oh, ow)} "
                                    "with target_res unset")
                             raise RuntimeError(msg)
-                        hotpath.check(lib.cc_nv12_to_rgb_resize(
+                        hotpath.yuv_to_rgb_resize(
                             f.y, f.uv, 1, fh, fw, f.pitch,
                             rgb[slot].data_ptr(), oh, ow, stream,
-                        ))
+                            bit_depth=int(fmt.bit_depth), matrix=matrix,
+                            full_range=full_range,
+                        )
                         filled[slot] = True
                         launched = True
                     if launched:

@@ -136,8 +136,9 @@ def _get_filtered_scenes(
 class VideoFrameExtractionStage(CuratorStage):
     """Whole-video decode to (N,27,48,3) u8 (frame_extraction_stages.py:71).
 
-    Raw-NV12 payloads run the fused HIP NV12->RGB+resize kernel at the
-    27x48 target; H.264 needs rocDecode (recorded error when absent).
+    Raw NV12 (8-bit) and P016 (10/12-bit) payloads run the fused HIP
+    YUV->RGB+resize kernel at the 27x48 target (BT.601 limited range);
+    H.264 needs rocDecode (recorded error when absent).
     """
 
     def __init__(self, *, num_cpus_per_worker: float = 3.0,
@@ -152,7 +153,7 @@ class VideoFrameExtractionStage(CuratorStage):
         return CuratorStageResource(cpus=self._num_cpus, gpus=0.25)
 
     def process_data(self, tasks: list[SplitPipeTask]) -> list[SplitPipeTask] | None:
-        lib = hotpath.require_gpu()
+        hotpath.require_gpu()
         for task in tasks:
             self._timer.reinit(self, task.get_major_size())
             for video in task.videos:
@@ -169,15 +170,16 @@ class VideoFrameExtractionStage(CuratorStage):
                     idx = np.arange(n, dtype=np.int32)
                     ys, uvs = raw_backend.frame_planes(raw, idx)
                     dev = torch.device("cuda")
-                    y_dev = torch.from_numpy(ys).to(dev)
-                    uv_dev = torch.from_numpy(uvs).to(dev)
+                    y_dev = torch.from_numpy(ys.view(np.uint8)).to(dev)
+                    uv_dev = torch.from_numpy(uvs.view(np.uint8)).to(dev)
                     out = torch.empty((n, 27, 48, 3), dtype=torch.uint8, device=dev)
                     stream = torch.cuda.current_stream(dev).cuda_stream
-                    hotpath.check(
-                        lib.cc_nv12_to_rgb_resize(
-                            y_dev.data_ptr(), uv_dev.data_ptr(), n, h, w, w,
-                            out.data_ptr(), 27, 48, stream,
-                        )
+                    # BT.601 limited for every input, 10/12-bit payloads
+                    # included (the reference's fixed conversion)
+                    depth, _, _, bps = raw_backend.parse_format(raw)
+                    hotpath.yuv_to_rgb_resize(
+                        y_dev.data_ptr(), uv_dev.data_ptr(), n, h, w, w * bps,
+                        out.data_ptr(), 27, 48, stream, bit_depth=depth,
                     )
                     arr = out.cpu().numpy()
                     video.frame_array = LazyData(value=arr, nbytes=arr.nbytes)

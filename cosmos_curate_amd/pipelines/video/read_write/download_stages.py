@@ -55,7 +55,8 @@ class VideoDownloader(CuratorStage):
         video.metadata.num_frames = n
         video.metadata.duration = n / fps
         video.metadata.video_codec = "raw"
-        video.metadata.pixel_format = "nv12"
+        depth = raw_backend.parse_format(raw)[0]
+        video.metadata.pixel_format = {8: "nv12", 10: "p010le", 12: "p012le"}[depth]
         video.timestamps = raw_backend.timestamps(raw)
 
     def _process_video(self, video: Video) -> None:

@@ -101,13 +101,29 @@ int  cc_decode_session_create(int device, int32_t codec, cc_decode_t** out);
 /* One AnnexB access unit (cc_demux_packet output) per call; pkt == NULL
  * flushes the stream (end-of-stream). */
 int  cc_decode_submit(cc_decode_t* s, const uint8_t* pkt, size_t size, int64_t pts);
-/* Mapped NV12 surfaces land as {y_ptr, uv_ptr, pitch} triples (HIP device
- * pointers into the decoder's surface pool).  Surfaces stay valid until
+/* Mapped NV12 (8-bit) or P016 (10/12-bit) surfaces land as {y_ptr, uv_ptr,
+ * pitch} triples (HIP device pointers into the decoder's surface pool;
+ * pitch in bytes, shared by both planes).  Surfaces stay valid until
  * cc_decode_recycle; consume them (launch + synchronize) first. */
 typedef struct cc_nv12_frame {
   void* y; void* uv; size_t pitch; int64_t pts; uint32_t width, height;
 } cc_nv12_frame;
 int  cc_decode_map_frames(cc_decode_t* s, cc_nv12_frame* out, size_t cap, size_t* n);
+/* What the stream's sequence header signalled (PyNvVideoCodec exposes the
+ * same through the decoder's format query, nvcodec_utils.py:199-313).
+ * 8-bit streams are mapped as NV12 surfaces (bytes_per_sample 1), 10- and
+ * 12-bit streams as P016 (u16 samples, MSB-aligned, bytes_per_sample 2);
+ * cc_nv12_frame keeps its layout for both and `pitch` stays in BYTES.
+ * chroma_format: 1 = 4:2:0 (rocDecVideoChromaFormat values).
+ * matrix_coefficients: the H.273 code (1 BT.709, 5/6 BT.601, 9 BT.2020-NCL,
+ * 2 unspecified); full_range: video_full_range_flag.  Valid after the
+ * first sequence callback (i.e. once a submit has reached the SPS);
+ * CC_ERR_INVALID before that. */
+typedef struct cc_stream_format {
+  int32_t bit_depth, chroma_format, matrix_coefficients, full_range,
+      bytes_per_sample;
+} cc_stream_format;
+int  cc_decode_stream_format(const cc_decode_t* s, cc_stream_format* out);
 /* Return every surface handed out by map_frames to the decoder pool
  * (rocDecParserMarkFrameForReuse).  Call after the consuming kernels
  * complete. */
@@ -131,6 +147,36 @@ int cc_nv12_to_rgb_resize(const void* y, const void* uv, int n,
 /* Plain NV12 -> RGB888 full resolution (the cvtcolor_into twin). */
 int cc_nv12_to_rgb(const void* y, const void* uv, int n,
                    int h, int w, size_t pitch, void* out_rgb, uint64_t stream);
+/* 8/10/12-bit 4:2:0 semi-planar -> RGB888 NHWC at full resolution with a
+ * selectable matrix and range: the cvcuda.cvtcolor_into(YUV2RGB_NV12) call
+ * (nvcodec_utils.py:178) for surfaces and colour standards that fixed
+ * 8-bit BT.601 conversion cannot express.
+ *   bit_depth   8 = u8 samples (NV12); 10 | 12 = u16 samples, MSB-aligned
+ *               (P016, what rocDecode emits; the low 16-depth bits are
+ *               ignored)
+ *   matrix      0 = BT.601, 1 = BT.709, 2 = BT.2020-NCL
+ *   full_range  0 = limited (16..235 / 16..240 scaled), 1 = full
+ * Frame f's Y plane starts at y + f*pitch_bytes*h, its UV plane at
+ * uv + f*pitch_bytes*(h/2).  f32 arithmetic, bit-exact vs tests/yuv_ref.py;
+ * (8, 0, 0) is bit-identical to cc_nv12_to_rgb.  Planes and pitch that
+ * are 16-byte aligned take the vectorised path (8 pixels per lane);
+ * anything else, and w % 8 row tails, a scalar one.  CC_ERR_INVALID on odd
+ * h/w, out-of-set bit_depth/matrix/full_range, pitch_bytes <
+ * w*bytes_per_sample, an odd pitch or pointer at 16 bit, null pointers or
+ * non-positive sizes — before any launch. */
+int cc_yuv420sp_to_rgb(const void* y, const void* uv, int n, int h, int w,
+                       size_t pitch_bytes, int bit_depth, int matrix,
+                       int full_range, void* out_rgb, uint64_t stream);
+/* The same conversion fused with the bilinear resize
+ * (cvcuda.resize_into(LINEAR), nvcodec_utils.py:189-194): each of the four
+ * taps is converted and rounded to u8 first — bit-identical to
+ * cc_yuv420sp_to_rgb followed by cc_resize_bilinear_u8, and (8, 0, 0) is
+ * bit-identical to cc_nv12_to_rgb_resize. */
+int cc_yuv420sp_to_rgb_resize(const void* y, const void* uv, int n,
+                              int src_h, int src_w, size_t pitch_bytes,
+                              int bit_depth, int matrix, int full_range,
+                              void* out_rgb, int out_h, int out_w,
+                              uint64_t stream);
 /* u8 NHWC bilinear resize (cvcuda LINEAR semantics). */
 int cc_resize_bilinear_u8(const void* in, int n, int src_h, int src_w,
                           void* out, int dst_h, int dst_w, uint64_t stream);

@@ -2,15 +2,25 @@
 // wiring without VCN hardware (tests/test_decode_session.py builds this
 // and injects it via LD_LIBRARY_PATH in a subprocess).
 //
-// Simulates a 48x32 8-bit AVC stream against the PUBLIC rocDecode API
+// Simulates a 48x32 AVC stream (8-bit unless told otherwise, below) against the PUBLIC rocDecode API
 // (rocprofiler-sdk/rocdecode/details/*.h): the first data packet
 // triggers the sequence callback, every packet then triggers one decode
 // + one display callback; GetVideoFrame hands out distinct fake device
 // pointers.  Introspection counters are exported as mock_* symbols.
 //
+// Optional environment, read when a parser is created (nothing set = the
+// 8-bit stream above, unchanged):
+//   MOCK_ROCDEC_BIT_DEPTH   8 | 10 | 12 | ... -> bit_depth_*_minus8
+//   MOCK_ROCDEC_MATRIX      H.273 matrix_coefficients code
+//   MOCK_ROCDEC_FULL_RANGE  0 | 1 -> video_full_range_flag
+// The decoder accepts P016 output only for a high-bit-depth stream and NV12
+// only for an 8-bit one; 16-bit surfaces report a pitch of 128 bytes (48
+// u16 samples, padded) with the UV plane pitch x coded height after Y.
+//
 //   g++ -shared -fPIC -D__HIP_PLATFORM_AMD__ \
 //       -I/opt/rocm/include tools/mock_rocdecode.cpp -o librocdecode.so
 
+#include <cstdlib>
 #include <cstring>
 
 #define __HIP_PLATFORM_AMD__ 1
@@ -24,6 +34,9 @@ struct MockParser {
   int packets = 0;
   int pic_counter = 0;
   int dpb = 0;
+  int depth_minus8 = 0;
+  int matrix = 0;
+  int full_range = 0;
 };
 
 struct MockDecoder {
@@ -34,6 +47,12 @@ int g_reused = 0;       // MarkFrameForReuse calls
 int g_decoded = 0;      // DecodeFrame calls
 int g_destroyed = 0;    // parser+decoder destroys
 int g_eos_seen = 0;
+int g_output_format = -1;  // output_format of the last created decoder
+
+int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e && *e ? atoi(e) : dflt;
+}
 
 }  // namespace
 
@@ -44,6 +63,7 @@ int mock_reused(void) { return g_reused; }
 int mock_decoded(void) { return g_decoded; }
 int mock_destroyed(void) { return g_destroyed; }
 int mock_eos_seen(void) { return g_eos_seen; }
+int mock_output_format(void) { return g_output_format; }
 
 rocDecStatus rocDecCreateVideoParser(RocdecVideoParser* h,
                                      RocdecParserParams* p) {
@@ -53,6 +73,9 @@ rocDecStatus rocDecCreateVideoParser(RocdecVideoParser* h,
   auto* m = new MockParser();
   m->params = *p;
   m->dpb = (int)p->max_num_decode_surfaces;
+  m->depth_minus8 = env_int("MOCK_ROCDEC_BIT_DEPTH", 8) - 8;
+  m->matrix = env_int("MOCK_ROCDEC_MATRIX", 0);
+  m->full_range = env_int("MOCK_ROCDEC_FULL_RANGE", 0);
   *h = m;
   return ROCDEC_SUCCESS;
 }
@@ -80,6 +103,10 @@ rocDecStatus rocDecParseVideoData(RocdecVideoParser h,
     fmt.display_area.right = 48;
     fmt.display_area.bottom = 30;  // display crop (like 1088 -> 1080)
     fmt.chroma_format = rocDecVideoChromaFormat_420;
+    fmt.bit_depth_luma_minus8 = (uint8_t)m->depth_minus8;
+    fmt.bit_depth_chroma_minus8 = (uint8_t)m->depth_minus8;
+    fmt.video_signal_description.matrix_coefficients = (uint8_t)m->matrix;
+    fmt.video_signal_description.video_full_range_flag = m->full_range & 1;
     int r = m->params.pfn_sequence_callback(m->params.user_data, &fmt);
     if (r == 0) return ROCDEC_RUNTIME_ERROR;
     if (r > 1) m->dpb = r;
@@ -116,8 +143,11 @@ rocDecStatus rocDecParserMarkFrameForReuse(RocdecVideoParser h, int pic_idx) {
 rocDecStatus rocDecCreateDecoder(rocDecDecoderHandle* h,
                                  RocDecoderCreateInfo* info) {
   if (!h || !info || info->width == 0) return ROCDEC_INVALID_PARAMETER;
-  if (info->output_format != rocDecVideoSurfaceFormat_NV12)
-    return ROCDEC_NOT_SUPPORTED;
+  const rocDecVideoSurfaceFormat want = info->bit_depth_minus_8 > 0
+                                            ? rocDecVideoSurfaceFormat_P016
+                                            : rocDecVideoSurfaceFormat_NV12;
+  if (info->output_format != want) return ROCDEC_NOT_SUPPORTED;
+  g_output_format = (int)info->output_format;
   auto* d = new MockDecoder();
   d->info = *info;
   *h = d;
@@ -141,12 +171,19 @@ rocDecStatus rocDecGetVideoFrame(rocDecDecoderHandle h, int pic_idx,
                                  RocdecProcParams* proc) {
   if (!h || !planes || !pitch || !proc || pic_idx < 0)
     return ROCDEC_INVALID_PARAMETER;
+  const auto* d = (const MockDecoder*)h;
   planes[0] = (void*)(uintptr_t)(0x100000 + pic_idx * 0x10000);
-  planes[1] = (void*)(uintptr_t)(0x100000 + pic_idx * 0x10000 + 0x8000);
   planes[2] = nullptr;
-  pitch[0] = 64;
-  pitch[1] = 64;
   pitch[2] = 0;
+  if (d->info.bit_depth_minus_8 > 0) {
+    pitch[0] = 128;
+    pitch[1] = 128;
+    planes[1] = (void*)((uintptr_t)planes[0] + 128u * d->info.height);
+  } else {
+    pitch[0] = 64;
+    pitch[1] = 64;
+    planes[1] = (void*)(uintptr_t)(0x100000 + pic_idx * 0x10000 + 0x8000);
+  }
   return ROCDEC_SUCCESS;
 }
 

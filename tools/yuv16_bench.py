@@ -1,0 +1,97 @@
+"""Time cc_yuv420sp_to_rgb (10-bit P016) against cc_nv12_to_rgb (8-bit) on
+one MI355X, at the same geometry, alternating the two in one process.
+
+    python tools/yuv16_bench.py [--frames 8 --height 2160 --width 3840
+                                 --launches 30 --warmup 5] [--out LOG]
+
+Per-launch device time from HIP events around each launch on the current
+stream; prints (and with --out also writes) medians, spread, the achieved
+GB/s from the bytes the algorithm must move (Y + UV in, RGB out), and that
+rate as a fraction of the 6.29 TB/s measured copy rate.
+Needs a GPU; there is no fallback.
+"""
+
+from __future__ import annotations
+
+import argparse
+import pathlib
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
+
+from cosmos_curate_amd import hotpath  # noqa: E402
+
+COPY_RATE_GBS = 6290.0  # measured float4 copy rate, MI355X
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=8)
+    ap.add_argument("--height", type=int, default=2160)
+    ap.add_argument("--width", type=int, default=3840)
+    ap.add_argument("--launches", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    n, h, w = args.frames, args.height, args.width
+
+    lib = hotpath.require_gpu()
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev).manual_seed(0)
+    y8 = torch.randint(0, 256, (n, h, w), dtype=torch.uint8, device=dev, generator=g)
+    uv8 = torch.randint(0, 256, (n, h // 2, w), dtype=torch.uint8, device=dev, generator=g)
+    # 16-bit planes as bytes (2 per sample): any bit pattern is a valid sample
+    y16 = torch.randint(0, 256, (n, h, 2 * w), dtype=torch.uint8, device=dev, generator=g)
+    uv16 = torch.randint(0, 256, (n, h // 2, 2 * w), dtype=torch.uint8, device=dev,
+                         generator=g)
+    out8 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    out16 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+
+    def run_nv12() -> None:
+        hotpath.check(lib.cc_nv12_to_rgb(
+            y8.data_ptr(), uv8.data_ptr(), n, h, w, w, out8.data_ptr(), stream))
+
+    def run_p010() -> None:
+        hotpath.check(lib.cc_yuv420sp_to_rgb(
+            y16.data_ptr(), uv16.data_ptr(), n, h, w, 2 * w, 10, 1, 0,
+            out16.data_ptr(), stream))
+
+    legs = {"nv12_to_rgb (8-bit, bt601)": (run_nv12, 4.5),
+            "yuv420sp_to_rgb (10-bit, bt709)": (run_p010, 6.0)}
+    times: dict[str, list[float]] = {k: [] for k in legs}
+    for it in range(args.warmup + args.launches):
+        for name, (fn, _) in legs.items():  # alternate the two legs
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if it >= args.warmup:
+                times[name].append(e0.elapsed_time(e1))
+
+    lines = [f"geometry: {n} frames of {h}x{w}; {args.launches} launches each "
+             f"after {args.warmup} warm-up, alternating; device "
+             f"{torch.cuda.get_device_name(0)}"]
+    for name, (_, bytes_per_px) in legs.items():
+        t = np.array(times[name])
+        med = float(np.median(t))
+        gbs = n * h * w * bytes_per_px / (med * 1e-3) / 1e9
+        lines.append(
+            f"{name}: median {med:.4f} ms  min {t.min():.4f}  max {t.max():.4f}  "
+            f"p10 {np.percentile(t, 10):.4f}  p90 {np.percentile(t, 90):.4f}  | "
+            f"{bytes_per_px} B/px -> {gbs:.0f} GB/s = {gbs / COPY_RATE_GBS:.3f} of "
+            f"the {COPY_RATE_GBS / 1000:.2f} TB/s copy rate")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(args.out).write_text(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
