@@ -9,6 +9,7 @@ Per-file flags:
   arithmetic vs the numpy oracle (oracle/color.py); FMA contraction would
   change rounding.
 - cc_gemm.hip: default contraction (MFMA does the math anyway).
+- cc_motion.hip: integer arithmetic only; no floating-point flags matter.
 """
 
 from __future__ import annotations
@@ -33,6 +34,7 @@ SOURCES: list[tuple[str, list[str]]] = [
     ("cc_dedup.hip", [ARCH]),
     ("cc_ln.hip", [ARCH]),
     ("cc_attn.hip", [ARCH]),
+    ("cc_motion.hip", [ARCH]),
 ]
 
 

@@ -83,6 +83,10 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.cc_gather_frames_u8.argtypes = [
         c.c_void_p, c.c_int, c.c_size_t, c.c_void_p, c.c_void_p, c.c_int,
         c.c_int, c.c_void_p, c.c_uint64]
+    lib.cc_motion_estimate.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_size_t,
+        c.c_size_t, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_void_p,
+        c.c_uint64]
     lib.cc_gemm_bf16.argtypes = [
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64,
         c.c_void_p, c.c_int, c.c_uint64]
@@ -173,6 +177,31 @@ def yuv_to_rgb_resize(
         check(lib.cc_yuv420sp_to_rgb_resize(
             y, uv, n, src_h, src_w, pitch_bytes, bit_depth, matrix,
             int(bool(full_range)), out_rgb, out_h, out_w, stream))
+
+
+def estimate_motion(
+    cur_ptr: int, ref_ptr: int, n: int, h: int, w: int, pitch_bytes: int,
+    mv_out_ptr: int, stream: int, *,
+    frame_stride_bytes: int | None = None, bit_depth: int = 8,
+    search_range: int = 16, mv_lambda: int = 4, cost_out_ptr: int = 0,
+) -> None:
+    """Block-matching motion estimation of ``n`` (cur, ref) luma pairs on
+    device pointers (cc_motion_estimate): int16 (dx, dy) per 16x16 block
+    into ``mv_out_ptr`` [n, ceil(h/16), ceil(w/16), 2], optionally the
+    winning cost as uint32 into ``cost_out_ptr``.
+
+    ``frame_stride_bytes=None`` means densely stacked planes
+    (``pitch_bytes*h``).  ``bit_depth`` 8 reads one byte per sample, 10 and
+    12 two (P016).  No fallback: a failing call raises.
+    """
+    if bit_depth not in (8, 10, 12):
+        raise ValueError(f"bit_depth must be 8, 10 or 12, got {bit_depth}")
+    if frame_stride_bytes is None:
+        frame_stride_bytes = pitch_bytes * h
+    check(load().cc_motion_estimate(
+        cur_ptr, ref_ptr, n, h, w, pitch_bytes, frame_stride_bytes,
+        1 if bit_depth == 8 else 2, search_range, mv_lambda, mv_out_ptr,
+        cost_out_ptr or None, stream))
 
 
 class VideoInfo(ctypes.Structure):

@@ -180,14 +180,28 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
             AestheticFilterStage(score_threshold=args.aesthetic_threshold, log_stats=True)
         )
     if args.motion_filter != "disable":
-        # MV extraction itself sits behind the rocDecode seam (DESIGN.md
-        # §4): clips without decoded_motion_data record a loud per-clip
-        # error; the stage order and filter semantics mirror the
-        # reference (:1340-1376)
+        # MV extraction from codec side data sits behind the rocDecode seam
+        # (DESIGN.md §4): with --motion-vector-backend none, clips without
+        # decoded_motion_data record a loud per-clip error; `estimate`
+        # fills it by block matching on the luma.  The stage order and
+        # filter semantics mirror the reference (:1340-1376)
         from cosmos_curate_amd.pipelines.video.filtering.motion.motion_filter_stages import (
             MotionFilterStage,
         )
 
+        if args.motion_vector_backend == "estimate":
+            from cosmos_curate_amd.pipelines.video.filtering.motion.motion_estimation import (
+                MotionVectorEstimationStage,
+            )
+
+            stages.append(MotionVectorEstimationStage(
+                verbose=args.verbose,
+                log_stats=True,
+                target_fps=args.motion_decode_target_fps,
+                target_duration_ratio=args.motion_decode_target_duration_ratio,
+                search_range=args.motion_search_range,
+                mv_lambda=args.motion_estimate_lambda,
+            ))
         stages.append(MotionFilterStage(
             global_mean_threshold=args.motion_global_mean_threshold,
             per_patch_min_256_threshold=args.motion_per_patch_min_256_threshold,
@@ -238,6 +252,18 @@ def _setup_parser(parser: argparse.ArgumentParser) -> None:
     parser.add_argument("--motion-global-mean-threshold", type=float, default=0.00098)
     parser.add_argument("--motion-per-patch-min-256-threshold", type=float,
                         default=0.000001)
+    parser.add_argument("--motion-vector-backend", choices=["none", "estimate"],
+                        default="none",
+                        help="where the motion filter's vectors come from: "
+                        "none (clips must already carry them) or estimate "
+                        "(GPU block matching on the luma of raw payloads)")
+    parser.add_argument("--motion-decode-target-fps", type=float, default=2.0)
+    parser.add_argument("--motion-decode-target-duration-ratio", type=float,
+                        default=0.5)
+    parser.add_argument("--motion-search-range", type=int, default=16,
+                        help="block-matching search range in pixels, 1..32")
+    parser.add_argument("--motion-estimate-lambda", type=int, default=4,
+                        help="SAD cost per pixel of vector length, 0..255")
     parser.add_argument("--multi-cam", action="store_true",
                         help="input path holds UUID-named session dirs, one "
                         "task per session (fixed-stride only, reference :213)")

@@ -203,6 +203,39 @@ int cc_gather_frames_u8(const void* frames, int n_in, size_t frame_bytes,
                         const int32_t* idx, const int32_t* counts, int n_idx,
                         int total_out, void* out, uint64_t stream);
 
+/* ---- block-matching motion estimation (hand-written HIP, gfx950) ------
+ * Replaces the motion-vector source of the motion filter, decode_for_motion
+ * (pipelines/video/filtering/motion/motion_vector_backend.py:169-250), which
+ * reads vectors from the H.264 decoder's side data; rocDecode exposes none,
+ * so the per-block displacement field is estimated from luma instead.
+ * Full-search, full-pel, 16x16 blocks, `n` independent (cur, ref) luma
+ * pairs per launch: pair f reads cur + f*frame_stride_bytes and
+ * ref + f*frame_stride_bytes, rows pitch_bytes apart.  cur and ref may
+ * point into one allocation (consecutive frames: cur = ref + one frame).
+ * All-integer arithmetic, bit-exact vs tests/motion_est_ref.py:
+ *   Y8(s)  = s (bytes_per_sample 1) | s >> 8 (2: P016, MSB-aligned LE)
+ *   grid   nby = ceil(h/16), nbx = ceil(w/16)
+ *   C(y,x) = Y8(cur[min(y,h-1)][min(x,w-1)])
+ *   R(y,x) = Y8(ref[clamp(y,0,h-1)][clamp(x,0,w-1)])
+ *   SAD    = sum over the block's 16x16 (j,i) of
+ *            |C(16by+j, 16bx+i) - R(16by+j+dy, 16bx+i+dx)|
+ *   cost   = SAD + lambda*(|dx|+|dy|), dx,dy in [-search_range, search_range]
+ *   winner = lexicographic minimum of (cost, dx*dx+dy*dy, dy, dx)
+ * mv_out   int16  [n][nby][nbx][2] = the winner's (dx, dy)
+ * cost_out uint32 [n][nby][nbx]    = its cost; may be NULL
+ * No alignment beyond the sample size is assumed of cur, ref or the pitch.
+ * Before any launch: CC_ERR_INVALID on null cur/ref/mv_out, non-positive
+ * n/h/w, search_range outside 1..32, lambda outside 0..255,
+ * bytes_per_sample not 1 or 2, pitch_bytes < w*bytes_per_sample,
+ * frame_stride_bytes < pitch_bytes*h, an odd pitch, stride or pointer at
+ * 2 bytes per sample, mv_out not 2-byte or cost_out not 4-byte aligned;
+ * CC_ERR_UNSUPPORTED when the block grid does not fit one launch (more than
+ * 65535 block rows or pairs, or 2^24 blocks in all). */
+int cc_motion_estimate(const void* cur, const void* ref, int n, int h, int w,
+                       size_t pitch_bytes, size_t frame_stride_bytes,
+                       int bytes_per_sample, int search_range, int lambda,
+                       void* mv_out, void* cost_out, uint64_t stream);
+
 /* ---- ViT MFMA GEMMs -------------------------------------------------
  * Replace the cuBLAS GEMMs under CLIPModel.get_image_features
  * (models/clip.py:71): patch-embed-as-GEMM, QKV/out projections, MLP.
