@@ -41,8 +41,8 @@ SOURCES: list[tuple[str, list[str]]] = [
 def _needs_build(src: pathlib.Path, obj: pathlib.Path) -> bool:
     if not obj.exists():
         return True
-    dep = [src, CSRC / "cc_common.hpp", PKG.parent / "include" / "cc_hotpath.h"]
-    return any(d.stat().st_mtime > obj.stat().st_mtime for d in dep if d.exists())
+    dep = [src, *CSRC.glob("*.hpp"), PKG.parent / "include" / "cc_hotpath.h"]
+    return any(d.stat().st_mtime > obj.stat().st_mtime for d in dep)
 
 
 def build(verbose: bool = True) -> pathlib.Path:

@@ -11,11 +11,13 @@
 // bandwidth-bound elementwise kernels between GEMMs (one 206 MB round
 // trip per MLP layer at the bench shape).
 //
-// Design (cdna_hip_programming.md §5, step-3 ladder + measured fixes):
-//   - 128x128 block tile, BK=64, 256 threads = 4 waves (2x2), each wave a
-//     64x64 sub-tile = 4x4 MFMA fragments of 16x16.
-//   - global->LDS via __builtin_amdgcn_global_load_lds width 16,
-//     double-buffered, one barrier + vmcnt(0) per K-tile.
+// Two kernel bodies; which one a call runs, its grid and its epilogue are
+// decided by cc::gemm_plan (cc_gemm_plan.hpp) and nowhere else.
+//
+// Shared by both (cdna_hip_programming.md §5, step-3 ladder + measured
+// fixes):
+//   - BK=64 K-tiles, global->LDS via __builtin_amdgcn_global_load_lds
+//     width 16, double-buffered.
 //   - LDS image XOR-swizzled: the 16-byte slot for (row, k16) lives at
 //     k16 ^ (row & 7).  glds demands a lane-linear LDS destination, so the
 //     swizzle is applied to the per-lane GLOBAL source address (guide §5
@@ -27,30 +29,31 @@
 //     of nwg runs on XCD b%8, so adjacent output tiles share an XCD's L2.
 //   - M/N edges by clamped global loads + predicated stores; K % 64 == 0
 //     required (all ViT shapes comply).
+//
+// k_gemm_bf16 (128² body): 128x128 block tile, 256 threads = 4 waves
+// (2x2), each wave a 64x64 sub-tile = 4x4 MFMA fragments of 16x16; one
+// barrier + vmcnt(0) per K-tile; one tile per workgroup; scalar epilogue.
+// The only body that takes row strides for A and the residual.  Runs the
+// small and the strided launches.
+//
+// k_gemm_bf16_t256 (256² body): 256x256 block tile, 512 threads = 8 waves
+// (2x4), each wave 128x64; 8-phase schedule with counted vmcnt waits, a
+// persistent fleet of workgroups walking the tile list, and an LDS-staged
+// coalesced bf16 epilogue for fused launches.  Dense operands, K % 128 ==
+// 0 and K >= 256 only.  Runs every large ViT GEMM (details at the kernel).
 
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-#include <vector>
-
 #include "cc_common.hpp"
+#include "cc_gemm_plan.hpp"
 #include "cc_timing.hpp"
-
-#define CC_CHECK_HIP(expr)                                                   \
-  do {                                                                       \
-    hipError_t _e = (expr);                                                  \
-    if (_e != hipSuccess)                                                    \
-      return cc::set_error(CC_ERR_HIP, "%s failed: %s", #expr,               \
-                           hipGetErrorString(_e));                           \
-  } while (0)
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-constexpr int BM = 128, BN = 128, BK = 64;
+constexpr int BM = cc::GEMM_T128, BN = cc::GEMM_T128, BK = cc::GEMM_BK;
 constexpr int WM = 64, WN = 64;  // per-wave sub-tile (2x2 wave grid)
 constexpr int FRAG = 16;         // mfma 16x16x32
 constexpr int MFR = WM / FRAG;   // 4
@@ -70,8 +73,9 @@ template <int ACT>
 __device__ __forceinline__ float cc_act(float v) {
   if constexpr (ACT == 1)
     return v * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * v));
-  if constexpr (ACT == 2) {
+  if constexpr (ACT == 2) {  // tanh-gelu (SigLIP gelu_pytorch_tanh)
     // tanh(z) = 1 - 2/(e^{2z}+1): __expf+rcp beats libm tanhf
+    // (~80 us/launch at the SigLIP fc1 shape, r01_siglip_prof)
     float z = 0.7978845608028654f * (v + 0.044715f * v * v * v);
     float t = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * z) + 1.0f);
     return 0.5f * v * (1.0f + t);
@@ -79,17 +83,29 @@ __device__ __forceinline__ float cc_act(float v) {
   return v;
 }
 
-// stage one 32-row slice of a [rows x BK] bf16 tile into LDS via glds,
-// with the k16 ^ (row&7) source swizzle.  lds_base = this wave's slice.
-__device__ __forceinline__ void stage_slice(const __bf16* __restrict__ src,
-                                            long ld, long row0, long row_limit,
-                                            long k0, __bf16* lds_base,
-                                            int lane) {
+// XCD-aware bijective remap of a linear block id (guide §5.4): block b
+// ran on XCD b%8; give XCD x the contiguous tile range so its L2 sees
+// adjacent tiles.  q = nwg/8, r = nwg%8.
+__device__ __forceinline__ int xcd_remap(int orig, int nwg) {
+  int q = nwg >> 3, r = nwg & 7;
+  int xcd = orig & 7, lid = orig >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + lid;
+}
+
+// one wave stages CHUNKS x 8 rows of a [rows x BK] bf16 tile into LDS via
+// glds (1 KB per chunk), with the k16 ^ (row&7) source swizzle.  lds_base
+// = this wave's slice.  The 128² body stages 32-row slices (4 chunks), the
+// 256² body 16-row slices of a 128-row half-tile (2 chunks).
+template <int CHUNKS>
+__device__ __forceinline__ void stage_rows(const __bf16* __restrict__ src,
+                                           long ld, long row0, long row_limit,
+                                           long k0, __bf16* lds_base,
+                                           int lane) {
   const int lrow8 = lane >> 3;            // local row within each 8-row chunk
   const int slot = lane & 7;              // LDS 16B slot this lane fills
   const int gk16 = slot ^ lrow8;          // swizzle: global k16 feeding slot
 #pragma unroll
-  for (int j = 0; j < 4; j++) {  // 4 x 1KB chunks = 32 rows
+  for (int j = 0; j < CHUNKS; j++) {
     long grow = row0 + j * 8 + lrow8;
     grow = grow < 0 ? 0 : (grow >= row_limit ? row_limit - 1 : grow);
     const __bf16* gptr = src + grow * ld + k0 + (long)gk16 * 8;
@@ -126,15 +142,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
   const int wid = tid >> 6;
   const int waveM = wid >> 1, waveN = wid & 1;
 
-  // XCD-aware bijective remap of the linear block id (guide §5.4):
-  // b ran on XCD b%8; give XCD x the contiguous tile range so its L2
-  // sees adjacent tiles.  q = nwg/8, r = nwg%8.
   int orig = blockIdx.x;
-  if (do_remap) {
-    int q = nwg >> 3, r = nwg & 7;
-    int xcd = orig & 7, lid = orig >> 3;
-    orig = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + lid;
-  }
+  if (do_remap) orig = xcd_remap(orig, nwg);
   const long bm = (long)(orig / nbx) * BM;
   const long bn = (long)(orig % nbx) * BN;
 
@@ -144,8 +153,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
   f32x4 acc[MFR][NFR] = {};
 
   const long KT = K / BK;
-  stage_slice(A, lda, arow0, M, 0, AS(0) + 32 * wid * BK, lane);
-  stage_slice(B, K, brow0, N, 0, BS(0) + 32 * wid * BK, lane);
+  stage_rows<4>(A, lda, arow0, M, 0, AS(0) + 32 * wid * BK, lane);
+  stage_rows<4>(B, K, brow0, N, 0, BS(0) + 32 * wid * BK, lane);
 
   const int arow_frag = waveM * WM + (lane & 15);
   const int brow_frag = waveN * WN + (lane & 15);
@@ -174,8 +183,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
     }
     if (kt + 1 < KT) {
       const long k0 = (kt + 1) * BK;
-      stage_slice(A, lda, arow0, M, k0, AS(buf ^ 1) + 32 * wid * BK, lane);
-      stage_slice(B, K, brow0, N, k0, BS(buf ^ 1) + 32 * wid * BK, lane);
+      stage_rows<4>(A, lda, arow0, M, k0, AS(buf ^ 1) + 32 * wid * BK, lane);
+      stage_rows<4>(B, K, brow0, N, k0, BS(buf ^ 1) + 32 * wid * BK, lane);
     }
 #pragma unroll
     for (int g = 0; g < 2; g++)
@@ -214,15 +223,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
 #pragma unroll
         for (int r = 0; r < 4; r++) {
           const long row = crow_base + m * FRAG + r;
-          float v = acc[m][n][r] + bval;
-          if (ACT == 1) v = v * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * v));
-          if (ACT == 2) {  // tanh-gelu (SigLIP gelu_pytorch_tanh)
-            // tanh(z) = 1 - 2/(e^{2z}+1): __expf+rcp beats libm tanhf
-            // (~80 us/launch at the SigLIP fc1 shape, r01_siglip_prof)
-            float z = 0.7978845608028654f * (v + 0.044715f * v * v * v);
-            float t = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * z) + 1.0f);
-            v = 0.5f * v * (1.0f + t);
-          }
+          float v = cc_act<ACT>(acc[m][n][r] + bval);
           if constexpr (HAS_RES) v += rv[r];
           if (c_is_bf16)
             ((unsigned short*)C)[row * N + col] = f32_to_bf16_rne(v);
@@ -245,15 +246,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
       for (int r = 0; r < 4; r++) {
         const long row = crow_base + m * FRAG + r;
         if (row >= M) continue;
-        float v = acc[m][n][r] + bval;
-        if (ACT == 1) v = v * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * v));  // quick-gelu
-        if (ACT == 2) {  // tanh-gelu (SigLIP gelu_pytorch_tanh)
-          // tanh(z) = 1 - 2/(e^{2z}+1): __expf+rcp beats libm tanhf
-          // (~80 us/launch at the SigLIP fc1 shape, r01_siglip_prof)
-          float z = 0.7978845608028654f * (v + 0.044715f * v * v * v);
-          float t = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * z) + 1.0f);
-          v = 0.5f * v * (1.0f + t);
-        }
+        float v = cc_act<ACT>(acc[m][n][r] + bval);
         if constexpr (HAS_RES) v += (float)residual[row * ldr + col];
         if (c_is_bf16)
           ((unsigned short*)C)[row * N + col] = f32_to_bf16_rne(v);
@@ -262,146 +255,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
       }
     }
   }
-}
-
-// 32x32x16-fragment variant: same staging/swizzle/XCD remap, wave tile
-// 64x64 as 2x2 fragments of 32x32.  Measured (profiles/r01_gemm_variants):
-// +19-36% over the 16x16x32 body on the K=768 ViT shapes and +7% on big
-// squares (fewer, denser MFMAs: 2382 vs 2075 TF ceiling); the 16x16 body
-// keeps a small edge at K >= 2048 (patch-embed), so the launcher picks by K.
-template <int ACT, bool HAS_BIAS, bool HAS_RES>
-__global__ __launch_bounds__(256, 2) void k_gemm_bf16_w32(
-    const __bf16* __restrict__ A, const __bf16* __restrict__ B,
-    void* __restrict__ C, const float* __restrict__ bias,
-    const __bf16* __restrict__ residual, long M, long N, long K,
-    int c_is_bf16, int nbx, int nwg, int do_remap) {
-  __shared__ __bf16 lds[2 * (BM + BN) * BK];
-#define AS32(b) (lds + (b) * (BM * BK))
-#define BS32(b) (lds + 2 * (BM * BK) + (b) * (BN * BK))
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int waveM = wid >> 1, waveN = wid & 1;
-
-  int orig = blockIdx.x;
-  if (do_remap) {
-    int q = nwg >> 3, r = nwg & 7;
-    int xcd = orig & 7, lid = orig >> 3;
-    orig = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + lid;
-  }
-  const long bm = (long)(orig / nbx) * BM;
-  const long bn = (long)(orig % nbx) * BN;
-  const long arow0 = bm + 32 * wid;
-  const long brow0 = bn + 32 * wid;
-
-  f32x16 acc[2][2] = {};
-  const long KT = K / BK;
-  stage_slice(A, K, arow0, M, 0, AS32(0) + 32 * wid * BK, lane);
-  stage_slice(B, K, brow0, N, 0, BS32(0) + 32 * wid * BK, lane);
-  const int arow = waveM * WM + (lane & 31);
-  const int brow = waveN * WN + (lane & 31);
-  int buf = 0;
-  // NOTE: the v9 register-double-buffer restructure (16x16 body above)
-  // was tried here too and measured SLOWER (qkv 570 vs 582 TF,
-  // profiles/r01_v9_graduated.log) — the w32 body keeps the per-k-step
-  // form, and the default dispatch no longer selects it (see launcher).
-  for (long kt = 0; kt < KT; ++kt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (kt + 1 < KT) {
-      const long k0 = (kt + 1) * BK;
-      stage_slice(A, K, arow0, M, k0, AS32(buf ^ 1) + 32 * wid * BK, lane);
-      stage_slice(B, K, brow0, N, k0, BS32(buf ^ 1) + 32 * wid * BK, lane);
-    }
-    const __bf16* At = AS32(buf);
-    const __bf16* Bt = BS32(buf);
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += 16) {
-      // 32x32x16 A/B fragment: lane l holds row l&31, k 8*(l>>5)..+8
-      const int k16 = (kk >> 3) + (lane >> 5);
-      bf16x8 a0 = frag_read(At, arow, k16);
-      bf16x8 a1 = frag_read(At, arow + 32, k16);
-      bf16x8 b0 = frag_read(Bt, brow, k16);
-      bf16x8 b1 = frag_read(Bt, brow + 32, k16);
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    buf ^= 1;
-  }
-  // C/D map 32x32x16: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-  const long col0 = bn + waveN * WN + (lane & 31);
-  const long row0 = bm + waveM * WM + 4 * (lane >> 5);
-  const bool interior = (bm + BM <= M) && (bn + BN <= N);
-  if (interior) {
-#pragma unroll
-    for (int m = 0; m < 2; m++) {
-#pragma unroll
-      for (int n = 0; n < 2; n++) {
-        const long col = col0 + n * 32;
-        float bval = 0.0f;
-        if constexpr (HAS_BIAS) bval = bias[col];
-        float rv[16];
-        if constexpr (HAS_RES) {
-#pragma unroll
-          for (int reg = 0; reg < 16; reg++)
-            rv[reg] = (float)residual[
-                (row0 + m * 32 + (reg & 3) + 8 * (reg >> 2)) * N + col];
-        }
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-          const long row = row0 + m * 32 + (reg & 3) + 8 * (reg >> 2);
-          float v = acc[m][n][reg] + bval;
-          if (ACT == 1) v = v * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * v));
-          if (ACT == 2) {  // tanh-gelu (SigLIP gelu_pytorch_tanh)
-            // tanh(z) = 1 - 2/(e^{2z}+1): __expf+rcp beats libm tanhf
-            // (~80 us/launch at the SigLIP fc1 shape, r01_siglip_prof)
-            float z = 0.7978845608028654f * (v + 0.044715f * v * v * v);
-            float t = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * z) + 1.0f);
-            v = 0.5f * v * (1.0f + t);
-          }
-          if constexpr (HAS_RES) v += rv[reg];
-          if (c_is_bf16)
-            ((unsigned short*)C)[row * N + col] = f32_to_bf16_rne(v);
-          else
-            ((float*)C)[row * N + col] = v;
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int m = 0; m < 2; m++) {
-#pragma unroll
-    for (int n = 0; n < 2; n++) {
-      const long col = col0 + n * 32;
-      if (col >= N) continue;
-      float bval = 0.0f;
-      if constexpr (HAS_BIAS) bval = bias[col];
-#pragma unroll
-      for (int reg = 0; reg < 16; reg++) {
-        const long row = row0 + m * 32 + (reg & 3) + 8 * (reg >> 2);
-        if (row >= M) continue;
-        float v = acc[m][n][reg] + bval;
-        if (ACT == 1) v = v * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * v));
-        if (ACT == 2) {  // tanh-gelu (SigLIP gelu_pytorch_tanh)
-          // tanh(z) = 1 - 2/(e^{2z}+1): __expf+rcp beats libm tanhf
-          // (~80 us/launch at the SigLIP fc1 shape, r01_siglip_prof)
-          float z = 0.7978845608028654f * (v + 0.044715f * v * v * v);
-          float t = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * z) + 1.0f);
-          v = 0.5f * v * (1.0f + t);
-        }
-        if constexpr (HAS_RES) v += (float)residual[row * N + col];
-        if (c_is_bf16)
-          ((unsigned short*)C)[row * N + col] = f32_to_bf16_rne(v);
-        else
-          ((float*)C)[row * N + col] = v;
-      }
-    }
-  }
-#undef AS32
-#undef BS32
+#undef AS
+#undef BS
 }
 
 // ---- 256x256 8-phase template kernel (guide "The 256² 8-phase
@@ -412,35 +267,15 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16_w32(
 // phases; COUNTED vmcnt(4) publishes at tile tops (B(t+2) spans each
 // boundary in flight); T19 scheduler weave of next-phase ds_reads into
 // the MFMA clusters; template-selected epilogue (LDS-staged coalesced
-// for fused bias/act/residual, scalar otherwise).  Serves every shape
-// whose 256-tile grid fills the fleet (the ViT GEMM mix; batch-64
-// per-shape TF in profiles/r02_gemm_v21.log + the epilogue-on numbers
-// in profiles/r02_epi_ab2.log).
-constexpr int BM2 = 256, BN2 = 256;
+// for fused bias/act/residual, scalar otherwise; EPI_STAGED is always
+// ACT != 0 || HAS_BIAS || HAS_RES).  Which shapes it serves is
+// cc::gemm_plan's rule (the ViT GEMM mix; batch-64 per-shape TF in
+// profiles/r02_gemm_v21.log + the epilogue-on numbers in
+// profiles/r02_epi_ab2.log).
+constexpr int BM2 = cc::GEMM_T256, BN2 = cc::GEMM_T256;
 constexpr int WM2 = 128, WN2 = 64;
 constexpr int MFR2 = WM2 / FRAG;  // 8
 constexpr int NFR2 = WN2 / FRAG;  // 4
-
-// one wave stages its 16-row slice of a 128-row half-tile: 2 glds.
-__device__ __forceinline__ void stage_half(const __bf16* __restrict__ src,
-                                           long ld, long row0,
-                                           long row_limit, long k0,
-                                           __bf16* lds_rowbase, int lane) {
-  const int lrow8 = lane >> 3;
-  const int slot = lane & 7;
-  const int gk16 = slot ^ lrow8;
-#pragma unroll
-  for (int j = 0; j < 2; j++) {
-    long grow = row0 + j * 8 + lrow8;
-    grow = grow < 0 ? 0 : (grow >= row_limit ? row_limit - 1 : grow);
-    const __bf16* gptr = src + grow * ld + k0 + (long)gk16 * 8;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)gptr,
-        (__attribute__((address_space(3))) unsigned int*)(lds_rowbase +
-                                                          j * 8 * BK),
-        16, 0, 0);
-  }
-}
 
 template <int ACT, bool HAS_BIAS, bool HAS_RES, bool EPI_STAGED>
 __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
@@ -466,29 +301,26 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
   const int lane = tid & 63;
   const int wid = tid >> 6;
   const int waveM = wid >> 2, waveN = wid & 3;
-  const long KT = K / BK;  // launcher guarantees even, >= 4
+  const long KT = K / BK;  // the plan guarantees even, >= 4
   const long srow = wid * 16;
   const int arow_base = waveM * WM2 + (lane & 15);
   const int brow_base = waveN * WN2 + (lane & 15);
   bf16x8 bfragT[NFR2][2];  // held for the whole K-tile
   bf16x8 afrag[2][2];      // one quadrant: 2 M-frags x 2 k-steps
 
+// one wave stages its 16-row slice of a 128-row half-tile: 2 glds.
 #define STAGE_A2(t, h)                                                      \
-  stage_half(A, K, bm + (h) * 128 + srow, M, (t) * BK,                      \
-             A2T((t) & 1) + ((h) * 128 + srow) * BK, lane)
+  stage_rows<2>(A, K, bm + (h) * 128 + srow, M, (t) * BK,                   \
+                A2T((t) & 1) + ((h) * 128 + srow) * BK, lane)
 #define STAGE_B2(t, h)                                                      \
-  stage_half(B, K, bn + (h) * 128 + srow, N, (t) * BK,                      \
-             B2T((t) & 1) + ((h) * 128 + srow) * BK, lane)
+  stage_rows<2>(B, K, bn + (h) * 128 + srow, N, (t) * BK,                   \
+                B2T((t) & 1) + ((h) * 128 + srow) * BK, lane)
 
   const int tiles = (nwg + (int)gridDim.x - 1) / (int)gridDim.x;
   long bm, bn;
   {
     int orig = (int)blockIdx.x;
-    if (order_mode == 1) {
-      int q = nwg >> 3, r = nwg & 7;
-      int xcd = orig & 7, lid = orig >> 3;
-      orig = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + lid;
-    }
+    if (order_mode == 1) orig = xcd_remap(orig, nwg);
     bm = (long)(orig / nbx) * BM2;
     bn = (long)(orig % nbx) * BN2;
   }
@@ -625,11 +457,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
     if (rep + 1 < tiles &&
         (int)blockIdx.x + (rep + 1) * (int)gridDim.x < nwg) {
       int orig = (int)blockIdx.x + (rep + 1) * (int)gridDim.x;
-      if (order_mode == 1) {
-        int q = nwg >> 3, r = nwg & 7;
-        int xcd = orig & 7, lid = orig >> 3;
-        orig = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + lid;
-      }
+      if (order_mode == 1) orig = xcd_remap(orig, nwg);
       bm = (long)(orig / nbx) * BM2;
       bn = (long)(orig % nbx) * BN2;
       STAGE_A2(0, 0);
@@ -755,186 +583,77 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
 #undef KTILE2
 }
 
-// Shared launcher.  lda / ldr are the row strides (elements) of A and of
-// the residual; a launch with lda != K or ldr != N is "strided" and
-// always runs the 128-tile body, the only one that carries the strides
-// (the persistent 256² loop stays dense: it is the hot kernel and the
-// strided launches are the small M = frames ones).
+struct GemmArgs {
+  const __bf16 *A, *B;
+  void* C;
+  const float* bias;
+  const __bf16* residual;
+  long M, N, K, lda, ldr;
+  int c_is_bf16;
+  hipStream_t stream;
+};
+
+// One launch per (ACT, HAS_BIAS, HAS_RES); the plan picks the body.  The
+// 256² epilogue is a TEMPLATE parameter fixed by the same three, not a
+// runtime branch: carrying both epilogues in one instantiation spilled
+// VGPRs in the rep loop and cost ~10% bare (profiles/r02_t19_sweep.log,
+// prod column vs the single-epilogue tool kernels).
+template <int ACT, bool HB, bool HR>
+void gemm_run(const cc_gemm_plan_info& p, const GemmArgs& g) {
+  const int nwg = p.tiles_x * p.tiles_y;
+  if (p.body == cc::GEMM_T256)
+    hipLaunchKernelGGL(
+        (k_gemm_bf16_t256<ACT, HB, HR, ACT != 0 || HB || HR>), dim3(p.grid),
+        dim3(p.block), 0, g.stream, g.A, g.B, g.C, g.bias, g.residual, g.M,
+        g.N, g.K, g.c_is_bf16, p.tiles_x, nwg, p.xcd_remap);
+  else
+    hipLaunchKernelGGL((k_gemm_bf16<ACT, HB, HR>), dim3(p.grid),
+                       dim3(p.block), 0, g.stream, g.A, g.B, g.C, g.bias,
+                       g.residual, g.M, g.N, g.K, g.lda, g.ldr, g.c_is_bf16,
+                       p.tiles_x, nwg, p.xcd_remap);
+}
+
+using GemmRunFn = void (*)(const cc_gemm_plan_info&, const GemmArgs&);
+constexpr GemmRunFn kGemmRun[3][2][2] = {  // [act][has_bias][has_residual]
+    {{gemm_run<0, false, false>, gemm_run<0, false, true>},
+     {gemm_run<0, true, false>, gemm_run<0, true, true>}},
+    {{gemm_run<1, false, false>, gemm_run<1, false, true>},
+     {gemm_run<1, true, false>, gemm_run<1, true, true>}},
+    {{gemm_run<2, false, false>, gemm_run<2, false, true>},
+     {gemm_run<2, true, false>, gemm_run<2, true, true>}}};
+
 int gemm_launch(const void* A, int64_t lda, const void* B, void* C, int64_t M,
                 int64_t N, int64_t K, const float* bias, int c_dtype, int act,
                 const void* residual, int64_t ldr, uint64_t stream) {
-  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0)
-    return cc::set_error(CC_ERR_INVALID, "bad gemm args");
-  if (K % BK != 0)
-    return cc::set_error(CC_ERR_UNSUPPORTED,
-                         "cc_gemm_bf16 requires K %% 64 == 0 (got %lld)",
-                         (long long)K);
-  if (!residual) ldr = N;
-  if (lda < K || ldr < N)
-    return cc::set_error(CC_ERR_INVALID,
-                         "gemm row stride below row length (lda %lld < K "
-                         "%lld or ldr %lld < N %lld)",
-                         (long long)lda, (long long)K, (long long)ldr,
-                         (long long)N);
-  if (lda % 8 != 0)
-    return cc::set_error(CC_ERR_INVALID,
-                         "gemm lda %lld breaks the 16-byte alignment of the "
-                         "direct-to-LDS loads (needs lda %% 8 == 0)",
-                         (long long)lda);
-  const bool strided = lda != K || ldr != N;
-  int nbx = (int)((N + BN - 1) / BN);
-  int nby = (int)((M + BM - 1) / BM);
-  int nwg = nbx * nby;
-  dim3 block(256);
-  dim3 grid(nwg);
+  if (!A || !B || !C) return cc::set_error(CC_ERR_INVALID, "bad gemm args");
+  cc_gemm_plan_info plan;
+  if (int rc = cc::gemm_plan(M, N, K, lda, ldr, bias != nullptr, act,
+                             residual != nullptr, cc::gemm_env_knobs(), &plan))
+    return rc;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = cc::timed_begin(stream, &ev0, &ev1);
-  // After the v9 register-double-buffer restructure the 16x16x32 body
-  // wins at EVERY measured shape (profiles/r01_v9_graduated.log: qkv
-  // 671 vs 570, squares 1051/1059 vs 1015/897 TF), so it is the default
-  // everywhere; the old K<2048 rule picked the 32x32x16 body.
-  // CC_GEMM_WIDE=1 re-enables the w32 body for A/B experiments.
-  static const int wide_env = [] {
-    const char* e = getenv("CC_GEMM_WIDE");
-    return e ? atoi(e) : -1;
-  }();
-  const bool wide = !strided && (wide_env >= 0 ? wide_env != 0 : false);
-  // 256² 8-phase template for the shapes its halved A/B re-read traffic
-  // pays on (measured profiles/r01_v10_b64.log: wins every shape with
-  // K>=1536 or N>=1536; loses only N=768 && K=768 at large M).
-  // CC_GEMM_TILE=0|1 forces the 128²/256² body for A/B experiments.
-  static const int tile_env = [] {
-    const char* e = getenv("CC_GEMM_TILE");
-    return e ? atoi(e) : -1;
-  }();
-  const bool t256_ok = (K % 128 == 0) && (K >= 256) && M > BM2 / 2;
-  // round-2: the t256 body is persistent (grid = min(nwg, 256)); it now
-  // also wins the N=768 && K=768 shape (out64 720 -> 796 TF,
-  // profiles/r02_gemm_persist.log), so the only shapes kept on the 128
-  // body are those whose 256-tile grid would underfill the persistent
-  // fleet (nwg256 < 256, e.g. the tiny visual-projection GEMM).
-  const int nbx2 = (int)((N + BN2 - 1) / BN2);
-  const int nby2 = (int)((M + BM2 - 1) / BM2);
-  const int nwg2 = nbx2 * nby2;
-  // Exception for the K-trigger at M = frames (the CLS-only last layer's
-  // fc2, N 768 / K 3072 at M 4704): 57 256-tiles leave most of the fleet
-  // idle where the 128 body has 222 tiles — measured 67.1 vs 53.1 us per
-  // launch, and 84.8 vs 67.6 us at the L/14 shape (76 vs 296 tiles),
-  // profiles/r03_gemm_small_m_ab.log.  Kept narrow: only when the
-  // 256-grid fills under half the fleet while the 128-grid fills at
-  // least half.  The N-trigger stays: fc1 at the same M (228 / 304
-  // 256-tiles) measured faster on the 256 body (29.7 vs 41.2 us).
-  const bool underfill = N < 1536 && nwg2 < 128 && nwg >= 128;
-  const bool t256 =
-      !wide && !strided && t256_ok &&
-      (tile_env >= 0
-           ? tile_env != 0
-           : ((K >= 1536 && !underfill) || N >= 1536 || nwg2 >= 256));
-  const bool hb = bias != nullptr;
-  const bool hr = residual != nullptr;
-  // XCD remap only for outputs that spill L3 (measured negative on the
-  // L2-resident ViT shapes, profiles/r01_opt3)
-  int remap = ((M * N) > (48LL << 20)) ? 1 : 0;
-  if (t256) {
-    nbx = nbx2;
-    nby = nby2;
-    nwg = nwg2;
-    // persistent fleet: 1 WG/CU; CC_GEMM_PERSIST=0 restores grid = nwg
-    // (one tile per WG) for A/B experiments.
-    static const int persist_env = [] {
-      const char* e = getenv("CC_GEMM_PERSIST");
-      return e ? atoi(e) : 1;
-    }();
-    grid = dim3(persist_env && nwg > 256 ? 256 : nwg);
-    block = dim3(512);
-    // stride + XCD remap order pays on skinny-N grids (row-band L2
-    // sharing: qkv/fc1/fc2/patch +9-13%); on wide grids plain stride
-    // wins (square8k 1295 vs 944 — profiles/r02_gemm_persist.log)
-    remap = nbx <= 16 ? 1 : 0;
-  }
-  // bf16 epilogue: LDS-staged coalesced when the launch fuses bias/act/
-  // residual (A/B: tower 582 -> 812 TF, bench 3184 -> 4188 clips/s,
-  // profiles/r02_epi_ab.log), scalar for bare C=A*B^T launches where the
-  // 4-pass staging is pure overhead (bare fc1 928 scalar vs 825 staged,
-  // profiles/r02_gemm_v20.log).  A TEMPLATE parameter, not a runtime
-  // branch: carrying both epilogues in one instantiation spilled VGPRs
-  // in the rep loop and cost ~10% bare (profiles/r02_t19_sweep.log,
-  // prod column vs the single-epilogue tool kernels).
-  // CC_GEMM_EPI=0|1 forces it for A/B.
-  static const int epi_env = [] {
-    const char* e = getenv("CC_GEMM_EPI");
-    return e ? atoi(e) : -1;
-  }();
-  const int epi_auto = (bias != nullptr || residual != nullptr || act != 0) ? 1 : 0;
-  const bool epi_staged = (epi_env >= 0 ? epi_env : epi_auto) != 0;
-#define CC_LAUNCH_GEMM(KER, A_, HB, HR)                                       \
-  hipLaunchKernelGGL((KER<A_, HB, HR>), grid, block, 0, (hipStream_t)stream,  \
-                     (const __bf16*)A, (const __bf16*)B, C, bias,             \
-                     (const __bf16*)residual, (long)M, (long)N, (long)K,      \
-                     c_dtype == 1 ? 1 : 0, nbx, nwg, remap)
-  // the 128-tile 16x16x32 body also takes the row strides
-#define CC_LAUNCH_GEMM_LD(KER, A_, HB, HR)                                    \
-  hipLaunchKernelGGL((KER<A_, HB, HR>), grid, block, 0, (hipStream_t)stream,  \
-                     (const __bf16*)A, (const __bf16*)B, C, bias,             \
-                     (const __bf16*)residual, (long)M, (long)N, (long)K,      \
-                     (long)lda, (long)ldr, c_dtype == 1 ? 1 : 0, nbx, nwg,    \
-                     remap)
-#define CC_LAUNCH_T256(A_, HB, HR)                                            \
-  do {                                                                        \
-    if (epi_staged)                                                           \
-      hipLaunchKernelGGL((k_gemm_bf16_t256<A_, HB, HR, true>), grid, block,   \
-                         0, (hipStream_t)stream, (const __bf16*)A,            \
-                         (const __bf16*)B, C, bias, (const __bf16*)residual,  \
-                         (long)M, (long)N, (long)K, c_dtype == 1 ? 1 : 0,     \
-                         nbx, nwg, remap);                                    \
-    else                                                                      \
-      hipLaunchKernelGGL((k_gemm_bf16_t256<A_, HB, HR, false>), grid, block,  \
-                         0, (hipStream_t)stream, (const __bf16*)A,            \
-                         (const __bf16*)B, C, bias, (const __bf16*)residual,  \
-                         (long)M, (long)N, (long)K, c_dtype == 1 ? 1 : 0,     \
-                         nbx, nwg, remap);                                    \
-  } while (0)
-#define CC_DISPATCH_ACT(L, KER, A_)                                           \
-  do {                                                                        \
-    if (hb && hr) L(KER, A_, true, true);                                     \
-    else if (hb) L(KER, A_, true, false);                                     \
-    else if (hr) L(KER, A_, false, true);                                     \
-    else L(KER, A_, false, false);                                            \
-  } while (0)
-#define CC_DISPATCH(L, KER)                                                   \
-  do {                                                                        \
-    if (act == 1) CC_DISPATCH_ACT(L, KER, 1);                                 \
-    else if (act == 2) CC_DISPATCH_ACT(L, KER, 2);  /* tanh-gelu (SigLIP) */  \
-    else CC_DISPATCH_ACT(L, KER, 0);                                          \
-  } while (0)
-  if (wide)
-    CC_DISPATCH(CC_LAUNCH_GEMM, k_gemm_bf16_w32);
-  else if (t256) {
-#define CC_DISPATCH_ACT_T256(A_)                                              \
-  do {                                                                        \
-    if (hb && hr) CC_LAUNCH_T256(A_, true, true);                             \
-    else if (hb) CC_LAUNCH_T256(A_, true, false);                             \
-    else if (hr) CC_LAUNCH_T256(A_, false, true);                             \
-    else CC_LAUNCH_T256(A_, false, false);                                    \
-  } while (0)
-    if (act == 1) CC_DISPATCH_ACT_T256(1);
-    else if (act == 2) CC_DISPATCH_ACT_T256(2);
-    else CC_DISPATCH_ACT_T256(0);
-#undef CC_DISPATCH_ACT_T256
-  } else
-    CC_DISPATCH(CC_LAUNCH_GEMM_LD, k_gemm_bf16);
-#undef CC_DISPATCH
-#undef CC_DISPATCH_ACT
-#undef CC_LAUNCH_GEMM
-#undef CC_LAUNCH_GEMM_LD
+  const GemmArgs args{(const __bf16*)A, (const __bf16*)B, C, bias,
+                      (const __bf16*)residual, (long)M, (long)N, (long)K,
+                      (long)lda, (long)ldr, c_dtype == 1 ? 1 : 0,
+                      (hipStream_t)stream};
+  // act: 1 quick-gelu, 2 tanh-gelu (SigLIP), anything else none
+  kGemmRun[act == 1 ? 1 : act == 2 ? 2 : 0][bias != nullptr]
+          [residual != nullptr](plan, args);
   hipError_t e = hipGetLastError();
   if (timed) cc::timed_end("gemm_bf16", stream, ev0, ev1);
   if (e != hipSuccess)
     return cc::set_error(CC_ERR_HIP, "gemm launch: %s", hipGetErrorString(e));
   return CC_OK;
 }
-
 }  // namespace
+
+extern "C" int cc_gemm_plan(int64_t M, int64_t N, int64_t K, int64_t lda,
+                            int64_t ldr, int has_bias, int act,
+                            int has_residual, cc_gemm_plan_info* out) {
+  if (!out) return cc::set_error(CC_ERR_INVALID, "cc_gemm_plan: null out");
+  return cc::gemm_plan(M, N, K, lda, ldr, has_bias != 0, act,
+                       has_residual != 0, cc::GemmKnobs{}, out);
+}
 
 extern "C" int cc_gemm_bf16_ex(const void* A, const void* B, void* C,
                                int64_t M, int64_t N, int64_t K,

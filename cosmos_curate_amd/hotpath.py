@@ -23,6 +23,20 @@ class HotpathUnavailableError(RuntimeError):
     """libcchot.so missing or unusable — the product GPU path must not run."""
 
 
+class GemmPlan(ctypes.Structure):
+    """cc_gemm_plan_info: how a GEMM call would be launched."""
+
+    _fields_ = [
+        ("body", ctypes.c_int32),
+        ("tiles_x", ctypes.c_int32),
+        ("tiles_y", ctypes.c_int32),
+        ("grid", ctypes.c_int32),
+        ("block", ctypes.c_int32),
+        ("xcd_remap", ctypes.c_int32),
+        ("epi_staged", ctypes.c_int32),
+    ]
+
+
 def _declare(lib: ctypes.CDLL) -> None:
     c = ctypes
     lib.cc_last_error.restype = c.c_char_p
@@ -97,6 +111,9 @@ def _declare(lib: ctypes.CDLL) -> None:
         c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
         c.c_int64, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_int64,
         c.c_uint64]
+    lib.cc_gemm_plan.argtypes = [
+        c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int,
+        c.c_int, c.c_int, c.POINTER(GemmPlan)]
 
     lib.cc_attn_cls.argtypes = [
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64,
@@ -202,6 +219,20 @@ def estimate_motion(
         cur_ptr, ref_ptr, n, h, w, pitch_bytes, frame_stride_bytes,
         1 if bit_depth == 8 else 2, search_range, mv_lambda, mv_out_ptr,
         cost_out_ptr or None, stream))
+
+
+def gemm_plan(
+    M: int, N: int, K: int, *, lda: int | None = None, ldr: int | None = None,
+    has_bias: bool = False, act: int = 0, has_residual: bool = False,
+) -> GemmPlan:
+    """The launch plan of a cc_gemm_bf16* call with these arguments
+    (cc_gemm_plan; default knobs, host-only).  ``lda`` / ``ldr`` default to
+    dense rows.  Raises on arguments the GEMM itself would reject."""
+    plan = GemmPlan()
+    check(load().cc_gemm_plan(
+        M, N, K, K if lda is None else lda, N if ldr is None else ldr,
+        int(has_bias), act, int(has_residual), ctypes.byref(plan)))
+    return plan
 
 
 class VideoInfo(ctypes.Structure):

@@ -265,6 +265,24 @@ int cc_gemm_bf16_strided(const void* A, int64_t lda, const void* B, void* C,
                          int c_dtype, int act, const void* residual,
                          int64_t ldr, uint64_t stream);
 
+/* How a cc_gemm_bf16* call with these arguments would be launched: the
+ * dispatch rule of the build (csrc/cc_gemm_plan.hpp), evaluated with the
+ * default knobs whatever the environment says.  Host-only, touches no
+ * device.  Validates like the GEMM entry points (same codes and
+ * cc_last_error text); ldr is ignored when has_residual is 0. */
+typedef struct cc_gemm_plan_info {
+  int32_t body;       /* 128 or 256: block tile of the kernel body */
+  int32_t tiles_x;    /* output tiles along N */
+  int32_t tiles_y;    /* output tiles along M */
+  int32_t grid;       /* workgroups launched (256² body: persistent fleet) */
+  int32_t block;      /* threads per workgroup */
+  int32_t xcd_remap;  /* 1 = tile order remapped for XCD L2 affinity */
+  int32_t epi_staged; /* 1 = LDS-staged bf16 epilogue (256² body only) */
+} cc_gemm_plan_info;
+int cc_gemm_plan(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldr,
+                 int has_bias, int act, int has_residual,
+                 cc_gemm_plan_info* out);
+
 /* ---- fused short-sequence attention (ViT encoder; replaces torch sdpa
  * + the qkv permute copies).  qkv = the fused-QKV GEMM output
  * [n*seq, 3*hidden] bf16; out [n*seq, hidden] bf16; seq <= 64, head dim

@@ -556,3 +556,47 @@ def test_gemm_bench_shape_parity(lib, M, N, K, act, res):
             y = y + r[r0:r0 + 64].float().cpu()
         torch.testing.assert_close(out[r0:r0 + 64].float().cpu(), y,
                                    rtol=2e-2, atol=8e-2)
+
+
+@pytest.mark.parametrize(
+    ("M", "N", "K", "act", "res", "body"),
+    [
+        # bias, f32 out.  256² body by the N trigger: one ragged row-tile,
+        # grid 6
+        (129, 1536, 256, 0, False, 256),
+        # bias + quick-gelu + residual, bf16 out.  6 x 43 = 258 tiles on the
+        # 256-WG fleet: two WGs walk a second tile, and the staged epilogue
+        # runs on the ragged last tile row
+        (10908, 1536, 256, 1, True, 256),
+        # bias + residual, bf16 out.  The `underfill` route onto the 128²
+        # body at a K that otherwise picks 256² (CLS-only last layer's fc2)
+        (4704, 768, 3072, 0, True, 128),
+    ],
+)
+def test_gemm_plan_matches_execution(lib, M, N, K, act, res, body):
+    """Each launcher branch at the smallest shape where it can go wrong:
+    the plan names the body, and the launch computes the right thing."""
+    plan = hotpath.gemm_plan(M, N, K, has_bias=True, act=act, has_residual=res)
+    assert plan.body == body
+    torch.manual_seed(M + N + K)
+    a = (torch.randn(M, K) * 0.5).to(torch.bfloat16).cuda()
+    b = (torch.randn(N, K) * 0.5).to(torch.bfloat16).cuda()
+    bias = torch.randn(N).float().cuda()
+    r = torch.randn(M, N).to(torch.bfloat16).cuda() if res else None
+    out_bf16 = bool(act or res)
+    out = torch.empty((M, N), device="cuda",
+                      dtype=torch.bfloat16 if out_bf16 else torch.float32)
+    stream = torch.cuda.current_stream().cuda_stream
+    hotpath.check(lib.cc_gemm_bf16_ex(
+        a.data_ptr(), b.data_ptr(), out.data_ptr(), M, N, K, bias.data_ptr(),
+        1 if out_bf16 else 0, act, r.data_ptr() if res else None, stream))
+    torch.cuda.synchronize()
+    y = a.float().cpu() @ b.float().cpu().T + bias.cpu()
+    if act == 1:
+        y = y * torch.sigmoid(1.702 * y)
+    if res:
+        y = y + r.float().cpu()
+    if out_bf16:
+        torch.testing.assert_close(out.float().cpu(), y, rtol=2e-2, atol=8e-2)
+    else:
+        torch.testing.assert_close(out.cpu(), y, rtol=5e-3, atol=5e-2)
