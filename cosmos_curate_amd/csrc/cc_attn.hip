@@ -641,18 +641,12 @@ extern "C" int cc_attn_cls(const void* q, const void* k, const void* v,
   if ((nwave + 3) / 4 > 0x7fffffffLL)
     return cc::set_error(CC_ERR_INVALID, "attn_cls grid too large");
   dim3 block(256), grid((unsigned)((nwave + 3) / 4));
-  hipEvent_t ev0, ev1;
-  bool timed = cc::timed_begin(stream, &ev0, &ev1);
-  hipLaunchKernelGGL(k_attn_cls, grid, block, 0, (hipStream_t)stream,
-                     (const __bf16*)q, (const __bf16*)k, (const __bf16*)v,
-                     (long)ldkv, (__bf16*)out, (long)n_frames, seq, heads,
-                     hidden, scale);
-  hipError_t e = hipGetLastError();
-  if (timed) cc::timed_end("attn_cls", stream, ev0, ev1);
-  if (e != hipSuccess)
-    return cc::set_error(CC_ERR_HIP, "attn_cls launch: %s",
-                         hipGetErrorString(e));
-  return CC_OK;
+  return cc::timed_launch("attn_cls", stream, [&] {
+    hipLaunchKernelGGL(k_attn_cls, grid, block, 0, (hipStream_t)stream,
+                       (const __bf16*)q, (const __bf16*)k, (const __bf16*)v,
+                       (long)ldkv, (__bf16*)out, (long)n_frames, seq, heads,
+                       hidden, scale);
+  });
 }
 
 extern "C" int cc_attn_small(const void* qkv, void* out, int64_t n_frames,
@@ -664,16 +658,11 @@ extern "C" int cc_attn_small(const void* qkv, void* out, int64_t n_frames,
     return cc::set_error(CC_ERR_UNSUPPORTED,
                          "cc_attn_small needs seq <= 64 and hd == 64");
   dim3 block(256), grid((unsigned)(n_frames * heads));
-  hipEvent_t ev0, ev1;
-  bool timed = cc::timed_begin(stream, &ev0, &ev1);
-  hipLaunchKernelGGL(k_attn_small, grid, block, 0, (hipStream_t)stream,
-                     (const __bf16*)qkv, (__bf16*)out, (long)n_frames, seq,
-                     heads, hidden, scale);
-  hipError_t e = hipGetLastError();
-  if (timed) cc::timed_end("attn_small", stream, ev0, ev1);
-  if (e != hipSuccess)
-    return cc::set_error(CC_ERR_HIP, "attn launch: %s", hipGetErrorString(e));
-  return CC_OK;
+  return cc::timed_launch("attn_small", stream, [&] {
+    hipLaunchKernelGGL(k_attn_small, grid, block, 0, (hipStream_t)stream,
+                       (const __bf16*)qkv, (__bf16*)out, (long)n_frames, seq,
+                       heads, hidden, scale);
+  });
 }
 
 extern "C" int cc_attn_mid(const void* qkv, void* out, int64_t n_frames,
@@ -685,16 +674,11 @@ extern "C" int cc_attn_mid(const void* qkv, void* out, int64_t n_frames,
     return cc::set_error(CC_ERR_UNSUPPORTED,
                          "cc_attn_mid needs 64 < seq <= 288 and hd == 64");
   dim3 block(256), grid((unsigned)(n_frames * heads));
-  hipEvent_t ev0, ev1;
-  bool timed = cc::timed_begin(stream, &ev0, &ev1);
-  hipLaunchKernelGGL(k_attn_mid, grid, block, 0, (hipStream_t)stream,
-                     (const __bf16*)qkv, (__bf16*)out, (long)n_frames, seq,
-                     heads, hidden, scale);
-  hipError_t e = hipGetLastError();
-  if (timed) cc::timed_end("attn_mid", stream, ev0, ev1);
-  if (e != hipSuccess)
-    return cc::set_error(CC_ERR_HIP, "attn_mid launch: %s", hipGetErrorString(e));
-  return CC_OK;
+  return cc::timed_launch("attn_mid", stream, [&] {
+    hipLaunchKernelGGL(k_attn_mid, grid, block, 0, (hipStream_t)stream,
+                       (const __bf16*)qkv, (__bf16*)out, (long)n_frames, seq,
+                       heads, hidden, scale);
+  });
 }
 
 extern "C" int cc_attn_flash(const void* qkv, void* out, int64_t n_frames,
@@ -708,14 +692,9 @@ extern "C" int cc_attn_flash(const void* qkv, void* out, int64_t n_frames,
                          "(use attn_small/attn_mid below that)");
   const int n_qtiles = (seq + 63) / 64;
   dim3 block(256), grid((unsigned)(n_frames * heads * (long)n_qtiles));
-  hipEvent_t ev0, ev1;
-  bool timed = cc::timed_begin(stream, &ev0, &ev1);
-  hipLaunchKernelGGL(k_attn_flash, grid, block, 0, (hipStream_t)stream,
-                     (const __bf16*)qkv, (__bf16*)out, (long)n_frames, seq,
-                     heads, hidden, scale);
-  hipError_t e = hipGetLastError();
-  if (timed) cc::timed_end("attn_flash", stream, ev0, ev1);
-  if (e != hipSuccess)
-    return cc::set_error(CC_ERR_HIP, "attn_flash launch: %s", hipGetErrorString(e));
-  return CC_OK;
+  return cc::timed_launch("attn_flash", stream, [&] {
+    hipLaunchKernelGGL(k_attn_flash, grid, block, 0, (hipStream_t)stream,
+                       (const __bf16*)qkv, (__bf16*)out, (long)n_frames, seq,
+                       heads, hidden, scale);
+  });
 }

@@ -630,20 +630,15 @@ int gemm_launch(const void* A, int64_t lda, const void* B, void* C, int64_t M,
   if (int rc = cc::gemm_plan(M, N, K, lda, ldr, bias != nullptr, act,
                              residual != nullptr, cc::gemm_env_knobs(), &plan))
     return rc;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = cc::timed_begin(stream, &ev0, &ev1);
   const GemmArgs args{(const __bf16*)A, (const __bf16*)B, C, bias,
                       (const __bf16*)residual, (long)M, (long)N, (long)K,
                       (long)lda, (long)ldr, c_dtype == 1 ? 1 : 0,
                       (hipStream_t)stream};
   // act: 1 quick-gelu, 2 tanh-gelu (SigLIP), anything else none
-  kGemmRun[act == 1 ? 1 : act == 2 ? 2 : 0][bias != nullptr]
-          [residual != nullptr](plan, args);
-  hipError_t e = hipGetLastError();
-  if (timed) cc::timed_end("gemm_bf16", stream, ev0, ev1);
-  if (e != hipSuccess)
-    return cc::set_error(CC_ERR_HIP, "gemm launch: %s", hipGetErrorString(e));
-  return CC_OK;
+  return cc::timed_launch("gemm_bf16", stream, [&] {
+    kGemmRun[act == 1 ? 1 : act == 2 ? 2 : 0][bias != nullptr]
+            [residual != nullptr](plan, args);
+  });
 }
 }  // namespace
 

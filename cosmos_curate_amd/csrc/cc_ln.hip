@@ -163,6 +163,17 @@ __global__ void k_layernorm_bf16_h128(const __bf16* __restrict__ x,
   *(bf16x2*)(yr + i0) = o;
 }
 
+// the CHUNK (= H / 64) values the two templates are instantiated for; the
+// entry points reject every other H before they launch, so the switches
+// below need no default
+#define CC_LN_CHUNKS(X) X(4) X(8) X(12) X(16) X(32) X(48) X(64)
+
+bool has_chunk(int64_t H) {
+#define OR_EQ(C) || H == 64 * C
+  return false CC_LN_CHUNKS(OR_EQ);
+#undef OR_EQ
+}
+
 }  // namespace
 
 extern "C" int cc_layernorm_bf16(const void* x, const void* w, const void* b,
@@ -174,16 +185,17 @@ extern "C" int cc_layernorm_bf16(const void* x, const void* w, const void* b,
     return cc::set_error(CC_ERR_UNSUPPORTED,
                          "H must be 128 or k*256, <=4096 (got %lld)",
                          (long long)H);
+  if (H != 128 && !has_chunk(H))
+    return cc::set_error(CC_ERR_UNSUPPORTED, "unsupported H %lld", (long long)H);
   dim3 block(256), grid((M + 3) / 4);
-  hipEvent_t ev0, ev1;
-  bool timed = cc::timed_begin(stream, &ev0, &ev1);
-  switch (H / 64) {
-    case 2:
-      hipLaunchKernelGGL(k_layernorm_bf16_h128, grid, block, 0,
-                         (hipStream_t)stream, (const __bf16*)x,
-                         (const float*)w, (const float*)b, (__bf16*)y,
-                         (long)M, eps);
-      break;
+  return cc::timed_launch("layernorm_bf16", stream, [&] {
+    switch (H / 64) {
+      case 2:
+        hipLaunchKernelGGL(k_layernorm_bf16_h128, grid, block, 0,
+                           (hipStream_t)stream, (const __bf16*)x,
+                           (const float*)w, (const float*)b, (__bf16*)y,
+                           (long)M, eps);
+        break;
 #define CASE(C)                                                            \
   case C:                                                                  \
     hipLaunchKernelGGL(k_layernorm_bf16<C>, grid, block, 0,                \
@@ -191,16 +203,10 @@ extern "C" int cc_layernorm_bf16(const void* x, const void* w, const void* b,
                        (const float*)w, (const float*)b, (__bf16*)y,       \
                        (long)M, (int)H, eps);                              \
     break;
-    CASE(4) CASE(8) CASE(12) CASE(16) CASE(32) CASE(48) CASE(64)
+        CC_LN_CHUNKS(CASE)
 #undef CASE
-    default:
-      return cc::set_error(CC_ERR_UNSUPPORTED, "unsupported H %lld", (long long)H);
-  }
-  hipError_t e = hipGetLastError();
-  if (timed) cc::timed_end("layernorm_bf16", stream, ev0, ev1);
-  if (e != hipSuccess)
-    return cc::set_error(CC_ERR_HIP, "layernorm launch: %s", hipGetErrorString(e));
-  return CC_OK;
+    }
+  });
 }
 
 extern "C" int cc_embed_assemble_ln(const void* tok, const void* cls,
@@ -214,11 +220,12 @@ extern "C" int cc_embed_assemble_ln(const void* tok, const void* cls,
   if (H % 256 != 0 || H > 64 * 64)
     return cc::set_error(CC_ERR_UNSUPPORTED, "H must be k*256, <=4096 (got %lld)",
                          (long long)H);
+  if (!has_chunk(H))
+    return cc::set_error(CC_ERR_UNSUPPORTED, "unsupported H %lld", (long long)H);
   const long nrows = (long)n_frames * tokens;
   dim3 block(256), grid((nrows + 3) / 4);
-  hipEvent_t ev0, ev1;
-  bool timed = cc::timed_begin(stream, &ev0, &ev1);
-  switch (H / 64) {
+  return cc::timed_launch("embed_assemble_ln", stream, [&] {
+    switch (H / 64) {
 #define CASE(C)                                                            \
   case C:                                                                  \
     hipLaunchKernelGGL(k_embed_assemble_ln<C>, grid, block, 0,             \
@@ -227,15 +234,8 @@ extern "C" int cc_embed_assemble_ln(const void* tok, const void* cls,
                        (const float*)w, (const float*)b, (__bf16*)y,       \
                        nrows, (int)tokens, (int)H, eps);                   \
     break;
-    CASE(4) CASE(8) CASE(12) CASE(16) CASE(32) CASE(48) CASE(64)
+      CC_LN_CHUNKS(CASE)
 #undef CASE
-    default:
-      return cc::set_error(CC_ERR_UNSUPPORTED, "unsupported H %lld", (long long)H);
-  }
-  hipError_t e = hipGetLastError();
-  if (timed) cc::timed_end("embed_assemble_ln", stream, ev0, ev1);
-  if (e != hipSuccess)
-    return cc::set_error(CC_ERR_HIP, "embed_assemble launch: %s",
-                         hipGetErrorString(e));
-  return CC_OK;
+    }
+  });
 }

@@ -199,26 +199,20 @@ int cc_motion_estimate(const void* cur, const void* ref, int n, int h, int w,
                          "blocks x %d pairs does not fit one launch", nbx, nby,
                          n);
   dim3 block(256), grid((unsigned)nbx, (unsigned)nby, (unsigned)n);
-  hipEvent_t ev0, ev1;
-  const bool timed = cc::timed_begin(stream, &ev0, &ev1);
-  if (bps == 1)
-    hipLaunchKernelGGL(k_motion_estimate<uint8_t>, grid, block, 0,
-                       (hipStream_t)stream, (const unsigned char*)cur,
-                       (const unsigned char*)ref, h, w, pitch_bytes,
-                       frame_stride_bytes, search_range, lambda,
-                       (short*)mv_out, (unsigned*)cost_out);
-  else
-    hipLaunchKernelGGL(k_motion_estimate<uint16_t>, grid, block, 0,
-                       (hipStream_t)stream, (const unsigned char*)cur,
-                       (const unsigned char*)ref, h, w, pitch_bytes,
-                       frame_stride_bytes, search_range, lambda,
-                       (short*)mv_out, (unsigned*)cost_out);
-  hipError_t e = hipGetLastError();
-  if (timed) cc::timed_end("motion_estimate", stream, ev0, ev1);
-  if (e != hipSuccess)
-    return cc::set_error(CC_ERR_HIP, "motion_estimate launch: %s",
-                         hipGetErrorString(e));
-  return CC_OK;
+  return cc::timed_launch("motion_estimate", stream, [&] {
+    if (bps == 1)
+      hipLaunchKernelGGL(k_motion_estimate<uint8_t>, grid, block, 0,
+                         (hipStream_t)stream, (const unsigned char*)cur,
+                         (const unsigned char*)ref, h, w, pitch_bytes,
+                         frame_stride_bytes, search_range, lambda,
+                         (short*)mv_out, (unsigned*)cost_out);
+    else
+      hipLaunchKernelGGL(k_motion_estimate<uint16_t>, grid, block, 0,
+                         (hipStream_t)stream, (const unsigned char*)cur,
+                         (const unsigned char*)ref, h, w, pitch_bytes,
+                         frame_stride_bytes, search_range, lambda,
+                         (short*)mv_out, (unsigned*)cost_out);
+  });
 }
 
 }  // extern "C"

@@ -19,8 +19,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include <vector>
 
 #include "cc_common.hpp"
@@ -36,31 +34,10 @@
 
 namespace {
 
-// BT.601 limited-range constants (oracle/color.py)
-__device__ __forceinline__ float3 yuv_to_rgb_f(float yf, float u, float v) {
-  const float CY = 1.1643835f, CVR = 1.5960267f, CVG = -0.8129676f,
-              CUG = -0.3917623f, CUB = 2.0172321f;
-  float fy = CY * yf;
-  return make_float3(fy + CVR * v, fy + CVG * v + CUG * u, fy + CUB * u);
-}
-
 __device__ __forceinline__ unsigned char round_u8(float x) {
   float r = floorf(x + 0.5f);
   r = fminf(fmaxf(r, 0.0f), 255.0f);
   return (unsigned char)r;
-}
-
-// convert one NV12 pixel (full-res coords) to rounded u8 RGB
-__device__ __forceinline__ uchar3 nv12_px(const unsigned char* __restrict__ y,
-                                          const unsigned char* __restrict__ uv,
-                                          int h, int w, size_t pitch, int yy,
-                                          int xx) {
-  float yf = (float)y[(size_t)yy * pitch + xx] - 16.0f;
-  size_t uvoff = (size_t)(yy >> 1) * pitch + (size_t)(xx & ~1);
-  float u = (float)uv[uvoff] - 128.0f;
-  float v = (float)uv[uvoff + 1] - 128.0f;
-  float3 rgb = yuv_to_rgb_f(yf, u, v);
-  return {round_u8(rgb.x), round_u8(rgb.y), round_u8(rgb.z)};
 }
 
 // pixel-center source coordinate (oracle/color.py:_src_grid)
@@ -69,75 +46,34 @@ __device__ __forceinline__ float src_coord(int d, int dst_n, int src_n) {
   return ((float)d + 0.5f) * scale - 0.5f;
 }
 
-// ---------------- NV12 -> RGB (full res) ----------------
-__global__ void k_nv12_to_rgb(const unsigned char* __restrict__ y,
-                              const unsigned char* __restrict__ uv, int n,
-                              int h, int w, size_t pitch,
-                              unsigned char* __restrict__ out) {
-  // one thread per pixel; NHWC u8 output, coalesced 3-byte stores via u8
-  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  long total = (long)n * h * w;
-  if (idx >= total) return;
-  int xx = idx % w;
-  long t = idx / w;
-  int yy = t % h;
-  int f = t / h;
-  const unsigned char* yp = y + (size_t)f * pitch * h;
-  const unsigned char* uvp = uv + (size_t)f * pitch * (h / 2);
-  uchar3 rgb = nv12_px(yp, uvp, h, w, pitch, yy, xx);
-  unsigned char* o = out + ((size_t)idx) * 3;
-  o[0] = rgb.x;
-  o[1] = rgb.y;
-  o[2] = rgb.z;
-}
+// The one bilinear definition every bilinear kernel shares; the f32
+// association order below is what keeps them bit-exact vs oracle/color.py:
+//   y0 = clip(floor(s), 0, n-1); y1 = min(y0+1, n-1); w = clip(s-y0, 0, 1)
+// with the clamp of y0 done in float.
+struct BilinearTaps {
+  int y0, y1, x0, x1;
+  float wy, wx;
+};
 
-// ---------------- fused NV12 -> RGB + bilinear resize ----------------
-// Equivalent to cvtcolor_into (u8 RGB materialized) followed by
-// resize_into(LINEAR): each tap is converted and rounded to u8 before the
-// f32 bilinear blend — bit-identical to the two-kernel sequence, without
-// writing the intermediate 1080p RGB to HBM.
-__global__ void k_nv12_to_rgb_resize(const unsigned char* __restrict__ y,
-                                     const unsigned char* __restrict__ uv,
-                                     int n, int sh, int sw, size_t pitch,
-                                     unsigned char* __restrict__ out, int dh,
-                                     int dw) {
-  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  long total = (long)n * dh * dw;
-  if (idx >= total) return;
-  int dx = idx % dw;
-  long t = idx / dw;
-  int dy = t % dh;
-  int f = t / dh;
-  const unsigned char* yp = y + (size_t)f * pitch * sh;
-  const unsigned char* uvp = uv + (size_t)f * pitch * (sh / 2);
-
+__device__ __forceinline__ BilinearTaps bilinear_taps(int dy, int dx, int dh,
+                                                      int dw, int sh, int sw) {
   float syf = src_coord(dy, dh, sh);
   float sxf = src_coord(dx, dw, sw);
-  // oracle: y0 = clip(floor(s), 0, n-1); y1 = min(y0+1, n-1); w = clip(s-y0,0,1)
-  int y0 = (int)fminf(fmaxf(floorf(syf), 0.0f), (float)(sh - 1));
-  int x0 = (int)fminf(fmaxf(floorf(sxf), 0.0f), (float)(sw - 1));
-  int y1 = min(y0 + 1, sh - 1);
-  int x1 = min(x0 + 1, sw - 1);
-  float wy = fminf(fmaxf(syf - (float)y0, 0.0f), 1.0f);
-  float wx = fminf(fmaxf(sxf - (float)x0, 0.0f), 1.0f);
+  BilinearTaps t;
+  t.y0 = (int)fminf(fmaxf(floorf(syf), 0.0f), (float)(sh - 1));
+  t.x0 = (int)fminf(fmaxf(floorf(sxf), 0.0f), (float)(sw - 1));
+  t.y1 = min(t.y0 + 1, sh - 1);
+  t.x1 = min(t.x0 + 1, sw - 1);
+  t.wy = fminf(fmaxf(syf - (float)t.y0, 0.0f), 1.0f);
+  t.wx = fminf(fmaxf(sxf - (float)t.x0, 0.0f), 1.0f);
+  return t;
+}
 
-  uchar3 p00 = nv12_px(yp, uvp, sh, sw, pitch, y0, x0);
-  uchar3 p01 = nv12_px(yp, uvp, sh, sw, pitch, y0, x1);
-  uchar3 p10 = nv12_px(yp, uvp, sh, sw, pitch, y1, x0);
-  uchar3 p11 = nv12_px(yp, uvp, sh, sw, pitch, y1, x1);
-
-  unsigned char* o = out + ((size_t)idx) * 3;
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    float v00 = (float)(c == 0 ? p00.x : c == 1 ? p00.y : p00.z);
-    float v01 = (float)(c == 0 ? p01.x : c == 1 ? p01.y : p01.z);
-    float v10 = (float)(c == 0 ? p10.x : c == 1 ? p10.y : p10.z);
-    float v11 = (float)(c == 0 ? p11.x : c == 1 ? p11.y : p11.z);
-    float top = v00 * (1.0f - wx) + v01 * wx;
-    float bot = v10 * (1.0f - wx) + v11 * wx;
-    float val = top * (1.0f - wy) + bot * wy;
-    o[c] = round_u8(val);
-  }
+__device__ __forceinline__ unsigned char bilinear_blend_u8(
+    float v00, float v01, float v10, float v11, float wx, float wy) {
+  float top = v00 * (1.0f - wx) + v01 * wx;
+  float bot = v10 * (1.0f - wx) + v11 * wx;
+  return round_u8(top * (1.0f - wy) + bot * wy);
 }
 
 // ---------------- 8/10/12-bit 4:2:0 semi-planar -> RGB ----------------
@@ -158,10 +94,10 @@ struct YuvCoef {
 // sc 255/224; full: yoff 0, CY = sc = 255*2^(d-8)/(2^d-1);
 // CVR 2(1-Kr)sc, CVG -2Kr(1-Kr)/Kg*sc, CUG -2Kb(1-Kb)/Kg*sc, CUB 2(1-Kb)sc.
 // Every row is the double-precision formula rounded to f32, EXCEPT BT.601
-// limited, which repeats yuv_to_rgb_f's literals verbatim (its CVR/CVG sit
-// one ulp off the formula; the 8-bit kernels and oracle/color.py are
-// pinned to them).
-const YuvCoef kYuvCoef[3][4] = {
+// limited: its five literals are the ones oracle/color.py uses, this row is
+// the only place they live here, and every 8-bit NV12 result is pinned to
+// them.  Its CVR/CVG sit one ulp off the formula and must not move.
+constexpr YuvCoef kYuvCoef[3][4] = {
     {{16.0f, 1.1643835f, 1.5960267f, -0.8129676f, -0.3917623f, 2.0172321f},
      {0.0f, 1.0f, 1.40199995f, -0.714136302f, -0.344136298f, 1.77199996f},
      {0.0f, 0.997067451f, 1.39788854f, -0.712042034f, -0.343127102f,
@@ -184,27 +120,49 @@ const YuvCoef kYuvCoef[3][4] = {
       1.87450838f}},
 };
 
+// what a kernel needs to convert one sample triple, as run-time values;
+// yuv420sp_launch is the one place that fills it in
+struct YuvParams {
+  int shift;
+  float scale;
+  YuvCoef k;
+};
+
+// (8, bt601, limited) as compile-time constants under YuvParams' member
+// names: the shift and the scale fold away and the coefficients become
+// immediates.  Only the fused resize kernel is instantiated with it — the
+// first kernel of bench.py's step, measurably slower with run-time values
+// (DESIGN.md §4a).
+struct YuvBt601Limited8 {
+  static constexpr int shift = 0;
+  static constexpr float scale = 1.0f;
+  static constexpr YuvCoef k = kYuvCoef[0][0];
+};
+
+// P = YuvParams or YuvBt601Limited8: one arithmetic definition for both
+template <typename P>
 __device__ __forceinline__ uchar3 yuv_to_rgb_u8(unsigned sy, unsigned su,
-                                                unsigned sv, int shift,
-                                                float scale,
-                                                const YuvCoef& k) {
-  float yf = (float)(sy >> shift) * scale - k.yoff;
-  float u = (float)(su >> shift) * scale - 128.0f;
-  float v = (float)(sv >> shift) * scale - 128.0f;
-  float fy = k.cy * yf;
-  return {round_u8(fy + k.cvr * v), round_u8(fy + k.cvg * v + k.cug * u),
-          round_u8(fy + k.cub * u)};
+                                                unsigned sv, const P& p) {
+  float yf = (float)(sy >> p.shift) * p.scale - p.k.yoff;
+  float u = (float)(su >> p.shift) * p.scale - 128.0f;
+  float v = (float)(sv >> p.shift) * p.scale - 128.0f;
+  float fy = p.k.cy * yf;
+  return {round_u8(fy + p.k.cvr * v),
+          round_u8(fy + p.k.cvg * v + p.k.cug * u),
+          round_u8(fy + p.k.cub * u)};
 }
 
 // one pixel (full-res coords); T = sample type, pitch in bytes
-template <typename T>
+template <typename T, typename P>
 __device__ __forceinline__ uchar3 yuv420sp_px(
     const unsigned char* __restrict__ y, const unsigned char* __restrict__ uv,
-    size_t pitch, int yy, int xx, int shift, float scale, const YuvCoef& k) {
+    size_t pitch, int yy, int xx, const P& p) {
   const T* yr = (const T*)(y + (size_t)yy * pitch);
-  const T* uvr = (const T*)(uv + (size_t)(yy >> 1) * pitch);
-  int cx = xx & ~1;
-  return yuv_to_rgb_u8(yr[xx], uvr[cx], uvr[cx + 1], shift, scale, k);
+  // the chroma pair through one pointer with constant offsets 0 and 1, so
+  // the compiler merges the two loads into one (8 loads per fused-resize
+  // thread where it would otherwise issue 12: +22 % time)
+  const T* c = (const T*)(uv + (size_t)(yy >> 1) * pitch) + (size_t)(xx & ~1);
+  return yuv_to_rgb_u8(yr[xx], c[0], c[1], p);
 }
 
 // Scalar path: one thread per pixel over columns [x_start, w) of every
@@ -214,8 +172,7 @@ template <typename T>
 __global__ void k_yuv420sp_to_rgb_px(const unsigned char* __restrict__ y,
                                      const unsigned char* __restrict__ uv,
                                      int n, int h, int w, int x_start,
-                                     size_t pitch, int shift, float scale,
-                                     YuvCoef k,
+                                     size_t pitch, YuvParams p,
                                      unsigned char* __restrict__ out) {
   long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int cw = w - x_start;
@@ -227,7 +184,7 @@ __global__ void k_yuv420sp_to_rgb_px(const unsigned char* __restrict__ y,
   int f = t / h;
   uchar3 rgb = yuv420sp_px<T>(y + (size_t)f * pitch * h,
                               uv + (size_t)f * pitch * (h / 2), pitch, yy, xx,
-                              shift, scale, k);
+                              p);
   unsigned char* o = out + (((size_t)f * h + yy) * w + xx) * 3;
   o[0] = rgb.x;
   o[1] = rgb.y;
@@ -249,7 +206,7 @@ template <typename T>
 __global__ void k_yuv420sp_to_rgb_v8(const unsigned char* __restrict__ y,
                                      const unsigned char* __restrict__ uv,
                                      int n, int h, int w, size_t pitch,
-                                     int shift, float scale, YuvCoef k,
+                                     YuvParams p,
                                      unsigned char* __restrict__ out) {
   constexpr int BITS = 8 * (int)sizeof(T);
   constexpr int PER = 32 / BITS;  // samples per dword
@@ -282,7 +239,7 @@ __global__ void k_yuv420sp_to_rgb_v8(const unsigned char* __restrict__ y,
     uchar3 rgb = yuv_to_rgb_u8((yw[j / PER] >> (BITS * (j % PER))) & MASK,
                                (cw[ju / PER] >> (BITS * (ju % PER))) & MASK,
                                (cw[jv / PER] >> (BITS * (jv % PER))) & MASK,
-                               shift, scale, k);
+                               p);
     o[(3 * j) >> 2] |= (unsigned)rgb.x << (8 * ((3 * j) & 3));
     o[(3 * j + 1) >> 2] |= (unsigned)rgb.y << (8 * ((3 * j + 1) & 3));
     o[(3 * j + 2) >> 2] |= (unsigned)rgb.z << (8 * ((3 * j + 2) & 3));
@@ -300,12 +257,15 @@ __global__ void k_yuv420sp_to_rgb_v8(const unsigned char* __restrict__ y,
   }
 }
 
-// Fused convert + bilinear resize, same definition as
-// k_nv12_to_rgb_resize: every tap converted and rounded to u8 first.
-template <typename T>
+// Fused convert + bilinear resize.  Equivalent to cvtcolor_into (u8 RGB
+// materialized) followed by resize_into(LINEAR): each tap is converted and
+// rounded to u8 before the f32 bilinear blend — bit-identical to
+// k_yuv420sp_to_rgb_* followed by k_resize_bilinear_u8, without writing
+// the intermediate full-resolution RGB to HBM.
+template <typename T, typename P>
 __global__ void k_yuv420sp_to_rgb_resize(
     const unsigned char* __restrict__ y, const unsigned char* __restrict__ uv,
-    int n, int sh, int sw, size_t pitch, int shift, float scale, YuvCoef k,
+    int n, int sh, int sw, size_t pitch, P p,
     unsigned char* __restrict__ out, int dh, int dw) {
   long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long total = (long)n * dh * dw;
@@ -317,32 +277,16 @@ __global__ void k_yuv420sp_to_rgb_resize(
   const unsigned char* yp = y + (size_t)f * pitch * sh;
   const unsigned char* uvp = uv + (size_t)f * pitch * (sh / 2);
 
-  float syf = src_coord(dy, dh, sh);
-  float sxf = src_coord(dx, dw, sw);
-  int y0 = (int)fminf(fmaxf(floorf(syf), 0.0f), (float)(sh - 1));
-  int x0 = (int)fminf(fmaxf(floorf(sxf), 0.0f), (float)(sw - 1));
-  int y1 = min(y0 + 1, sh - 1);
-  int x1 = min(x0 + 1, sw - 1);
-  float wy = fminf(fmaxf(syf - (float)y0, 0.0f), 1.0f);
-  float wx = fminf(fmaxf(sxf - (float)x0, 0.0f), 1.0f);
-
-  uchar3 p00 = yuv420sp_px<T>(yp, uvp, pitch, y0, x0, shift, scale, k);
-  uchar3 p01 = yuv420sp_px<T>(yp, uvp, pitch, y0, x1, shift, scale, k);
-  uchar3 p10 = yuv420sp_px<T>(yp, uvp, pitch, y1, x0, shift, scale, k);
-  uchar3 p11 = yuv420sp_px<T>(yp, uvp, pitch, y1, x1, shift, scale, k);
+  const BilinearTaps b = bilinear_taps(dy, dx, dh, dw, sh, sw);
+  uchar3 p00 = yuv420sp_px<T>(yp, uvp, pitch, b.y0, b.x0, p);
+  uchar3 p01 = yuv420sp_px<T>(yp, uvp, pitch, b.y0, b.x1, p);
+  uchar3 p10 = yuv420sp_px<T>(yp, uvp, pitch, b.y1, b.x0, p);
+  uchar3 p11 = yuv420sp_px<T>(yp, uvp, pitch, b.y1, b.x1, p);
 
   unsigned char* o = out + ((size_t)idx) * 3;
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    float v00 = (float)(c == 0 ? p00.x : c == 1 ? p00.y : p00.z);
-    float v01 = (float)(c == 0 ? p01.x : c == 1 ? p01.y : p01.z);
-    float v10 = (float)(c == 0 ? p10.x : c == 1 ? p10.y : p10.z);
-    float v11 = (float)(c == 0 ? p11.x : c == 1 ? p11.y : p11.z);
-    float top = v00 * (1.0f - wx) + v01 * wx;
-    float bot = v10 * (1.0f - wx) + v11 * wx;
-    float val = top * (1.0f - wy) + bot * wy;
-    o[c] = round_u8(val);
-  }
+  o[0] = bilinear_blend_u8(p00.x, p01.x, p10.x, p11.x, b.wx, b.wy);
+  o[1] = bilinear_blend_u8(p00.y, p01.y, p10.y, p11.y, b.wx, b.wy);
+  o[2] = bilinear_blend_u8(p00.z, p01.z, p10.z, p11.z, b.wx, b.wy);
 }
 
 // ---------------- u8 NHWC bilinear resize ----------------
@@ -359,26 +303,15 @@ __global__ void k_resize_bilinear_u8(const unsigned char* __restrict__ in,
   int f = t / dh;
   const unsigned char* src = in + (size_t)f * sh * sw * 3;
 
-  float syf = src_coord(dy, dh, sh);
-  float sxf = src_coord(dx, dw, sw);
-  int y0 = (int)fminf(fmaxf(floorf(syf), 0.0f), (float)(sh - 1));
-  int x0 = (int)fminf(fmaxf(floorf(sxf), 0.0f), (float)(sw - 1));
-  int y1 = min(y0 + 1, sh - 1);
-  int x1 = min(x0 + 1, sw - 1);
-  float wy = fminf(fmaxf(syf - (float)y0, 0.0f), 1.0f);
-  float wx = fminf(fmaxf(sxf - (float)x0, 0.0f), 1.0f);
-
+  const BilinearTaps b = bilinear_taps(dy, dx, dh, dw, sh, sw);
   unsigned char* o = out + ((size_t)idx) * 3;
 #pragma unroll
-  for (int c = 0; c < 3; c++) {
-    float v00 = src[((size_t)y0 * sw + x0) * 3 + c];
-    float v01 = src[((size_t)y0 * sw + x1) * 3 + c];
-    float v10 = src[((size_t)y1 * sw + x0) * 3 + c];
-    float v11 = src[((size_t)y1 * sw + x1) * 3 + c];
-    float top = v00 * (1.0f - wx) + v01 * wx;
-    float bot = v10 * (1.0f - wx) + v11 * wx;
-    o[c] = round_u8(top * (1.0f - wy) + bot * wy);
-  }
+  for (int c = 0; c < 3; c++)
+    o[c] = bilinear_blend_u8(src[((size_t)b.y0 * sw + b.x0) * 3 + c],
+                             src[((size_t)b.y0 * sw + b.x1) * 3 + c],
+                             src[((size_t)b.y1 * sw + b.x0) * 3 + c],
+                             src[((size_t)b.y1 * sw + b.x1) * 3 + c], b.wx,
+                             b.wy);
 }
 
 // ---------------- u8 NHWC bicubic resize (A=-0.75) ----------------
@@ -654,18 +587,109 @@ __global__ void k_gather_frames_u8(const unsigned char* __restrict__ frames,
   out[idx] = frames[(size_t)out_src[j] * frame_bytes + b];
 }
 
-// timing helpers (non-serializing; see cc_timing.hpp)
-inline int launch_timed(const char* name, uint64_t stream, hipEvent_t* evs,
-                        bool* timed) {
-  (void)name;
-  *timed = cc::timed_begin(stream, &evs[0], &evs[1]);
-  return 0;
+// ---------------- YUV launcher ----------------
+// argument checks of every YUV entry point (all before any launch)
+int yuv420sp_check(const void* y, const void* uv, const void* out, int n,
+                   int h, int w, size_t pitch, int bit_depth, int matrix,
+                   int full_range) {
+  if (!y || !uv || !out)
+    return cc::set_error(CC_ERR_INVALID, "yuv420sp: null pointer");
+  if (n <= 0 || h <= 0 || w <= 0)
+    return cc::set_error(CC_ERR_INVALID, "yuv420sp: non-positive size n=%d "
+                         "h=%d w=%d", n, h, w);
+  if ((h & 1) || (w & 1))
+    return cc::set_error(CC_ERR_INVALID,
+                         "yuv420sp: 4:2:0 needs even dims (got %dx%d)", w, h);
+  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12)
+    return cc::set_error(CC_ERR_INVALID,
+                         "yuv420sp: bit_depth must be 8, 10 or 12 (got %d)",
+                         bit_depth);
+  if (matrix < 0 || matrix > 2)
+    return cc::set_error(CC_ERR_INVALID, "yuv420sp: matrix must be 0 (bt601), "
+                         "1 (bt709) or 2 (bt2020) (got %d)", matrix);
+  if (full_range != 0 && full_range != 1)
+    return cc::set_error(CC_ERR_INVALID,
+                         "yuv420sp: full_range must be 0 or 1 (got %d)",
+                         full_range);
+  const size_t bps = bit_depth == 8 ? 1 : 2;
+  if (pitch < (size_t)w * bps)
+    return cc::set_error(CC_ERR_INVALID, "yuv420sp: pitch %zu < row bytes %zu",
+                         pitch, (size_t)w * bps);
+  if (bps == 2 && ((pitch | (size_t)y | (size_t)uv) & 1))
+    return cc::set_error(CC_ERR_INVALID, "yuv420sp: 16-bit planes need an "
+                         "even pitch and 2-byte-aligned pointers");
+  return CC_OK;
 }
 
-inline void finish_timed(const char* name, uint64_t stream, hipEvent_t* evs,
-                         bool timed) {
-  if (!timed) return;
-  cc::timed_end(name, stream, evs[0], evs[1]);
+// The launches of one checked call for sample type T: the fused kernel
+// when `resize`, else the vector body and/or the scalar kernel.
+template <typename T>
+int yuv420sp_run(const char* name, const unsigned char* y,
+                 const unsigned char* uv, int n, int h, int w, size_t pitch,
+                 const YuvParams& p, bool bt601_limited, unsigned char* out,
+                 bool resize, int out_h, int out_w, uint64_t stream) {
+  const hipStream_t s = (hipStream_t)stream;
+  const dim3 block(256);
+  auto blocks = [](long threads) {
+    return dim3((unsigned)((threads + 255) / 256));
+  };
+  if (resize)
+    return cc::timed_launch(name, stream, [&] {
+      const dim3 grid = blocks((long)n * out_h * out_w);
+      if constexpr (sizeof(T) == 1) {
+        if (bt601_limited) {
+          hipLaunchKernelGGL((k_yuv420sp_to_rgb_resize<T, YuvBt601Limited8>),
+                             grid, block, 0, s, y, uv, n, h, w, pitch,
+                             YuvBt601Limited8{}, out, out_h, out_w);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((k_yuv420sp_to_rgb_resize<T, YuvParams>), grid,
+                         block, 0, s, y, uv, n, h, w, pitch, p, out, out_h,
+                         out_w);
+    });
+  // 16-byte-aligned planes and pitch: 8-pixel runs go through the vector
+  // kernel and only the w % 8 row tails through the scalar one
+  const bool aligned = (((size_t)y | (size_t)uv | pitch) & 15) == 0;
+  const int x_vec = aligned ? (w / 8) * 8 : 0;
+  if (x_vec > 0) {
+    int rc = cc::timed_launch(name, stream, [&] {
+      hipLaunchKernelGGL(k_yuv420sp_to_rgb_v8<T>,
+                         blocks((long)n * h * (w / 8)), block, 0, s, y, uv, n,
+                         h, w, pitch, p, out);
+    });
+    if (rc != CC_OK) return rc;
+  }
+  if (x_vec < w)
+    return cc::timed_launch(name, stream, [&] {
+      hipLaunchKernelGGL(k_yuv420sp_to_rgb_px<T>,
+                         blocks((long)n * h * (w - x_vec)), block, 0, s, y, uv,
+                         n, h, w, x_vec, pitch, p, out);
+    });
+  return CC_OK;
+}
+
+// The one launcher behind cc_yuv420sp_to_rgb* and cc_nv12_to_rgb* (which
+// pass (8, 0, 0)): checks, the conversion parameters, and the choice of
+// instantiation.  `name` is the caller's timing name.
+int yuv420sp_launch(const char* name, const void* y, const void* uv, int n,
+                    int h, int w, size_t pitch, int bit_depth, int matrix,
+                    int full_range, void* out, bool resize, int out_h,
+                    int out_w, uint64_t stream) {
+  int rc = yuv420sp_check(y, uv, out, n, h, w, pitch, bit_depth, matrix,
+                          full_range);
+  if (rc != CC_OK) return rc;
+  if (resize && (out_h <= 0 || out_w <= 0))
+    return cc::set_error(CC_ERR_INVALID,
+                         "yuv420sp: non-positive output size %dx%d", out_w,
+                         out_h);
+  const YuvParams p{bit_depth == 8 ? 0 : 16 - bit_depth,
+                    1.0f / (float)(1 << (bit_depth - 8)),
+                    kYuvCoef[matrix][full_range ? 1 + (bit_depth - 8) / 2 : 0]};
+  auto run = bit_depth == 8 ? yuv420sp_run<uint8_t> : yuv420sp_run<uint16_t>;
+  return run(name, (const unsigned char*)y, (const unsigned char*)uv, n, h, w,
+             pitch, p, matrix == 0 && !full_range, (unsigned char*)out, resize,
+             out_h, out_w, stream);
 }
 
 }  // namespace
@@ -730,156 +754,34 @@ int cc_timing_report(const char* kernel, double* total_ms, int64_t* count) {
   return CC_OK;
 }
 
-#define CC_LAUNCH(name, grid, block, stream, kernel, ...)                   \
-  do {                                                                      \
-    hipEvent_t _evs[2];                                                     \
-    bool _timed;                                                            \
-    launch_timed(name, stream, _evs, &_timed);                              \
-    hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream,         \
-                       __VA_ARGS__);                                        \
-    hipError_t _e = hipGetLastError();                                      \
-    if (_e != hipSuccess)                                                   \
-      return cc::set_error(CC_ERR_HIP, "%s launch: %s", name,               \
-                           hipGetErrorString(_e));                          \
-    finish_timed(name, stream, _evs, _timed);                               \
-  } while (0)
-
 int cc_nv12_to_rgb(const void* y, const void* uv, int n, int h, int w,
                    size_t pitch, void* out_rgb, uint64_t stream) {
-  if (!y || !uv || !out_rgb || n <= 0 || h <= 0 || w <= 0 || pitch < (size_t)w)
-    return cc::set_error(CC_ERR_INVALID, "bad nv12 args");
-  if ((h & 1) || (w & 1))
-    return cc::set_error(CC_ERR_INVALID, "NV12 needs even dims (got %dx%d)", w, h);
-  long total = (long)n * h * w;
-  dim3 block(256), grid((total + 255) / 256);
-  CC_LAUNCH("nv12_to_rgb", grid, block, stream, k_nv12_to_rgb,
-            (const unsigned char*)y, (const unsigned char*)uv, n, h, w, pitch,
-            (unsigned char*)out_rgb);
-  return CC_OK;
+  return yuv420sp_launch("nv12_to_rgb", y, uv, n, h, w, pitch, 8, 0, 0,
+                         out_rgb, false, 0, 0, stream);
 }
 
 int cc_nv12_to_rgb_resize(const void* y, const void* uv, int n, int src_h,
                           int src_w, size_t pitch, void* out_rgb, int out_h,
                           int out_w, uint64_t stream) {
-  if (!y || !uv || !out_rgb || n <= 0 || src_h <= 0 || src_w <= 0 ||
-      out_h <= 0 || out_w <= 0 || pitch < (size_t)src_w)
-    return cc::set_error(CC_ERR_INVALID, "bad nv12_resize args");
-  if ((src_h & 1) || (src_w & 1))
-    return cc::set_error(CC_ERR_INVALID, "NV12 needs even dims (got %dx%d)",
-                         src_w, src_h);
-  long total = (long)n * out_h * out_w;
-  dim3 block(256), grid((total + 255) / 256);
-  CC_LAUNCH("nv12_to_rgb_resize", grid, block, stream, k_nv12_to_rgb_resize,
-            (const unsigned char*)y, (const unsigned char*)uv, n, src_h, src_w,
-            pitch, (unsigned char*)out_rgb, out_h, out_w);
-  return CC_OK;
-}
-
-// argument checks shared by the two cc_yuv420sp_* launchers (all before
-// any launch)
-static int yuv420sp_check(const void* y, const void* uv, const void* out,
-                          int n, int h, int w, size_t pitch, int bit_depth,
-                          int matrix, int full_range) {
-  if (!y || !uv || !out)
-    return cc::set_error(CC_ERR_INVALID, "yuv420sp: null pointer");
-  if (n <= 0 || h <= 0 || w <= 0)
-    return cc::set_error(CC_ERR_INVALID, "yuv420sp: non-positive size n=%d "
-                         "h=%d w=%d", n, h, w);
-  if ((h & 1) || (w & 1))
-    return cc::set_error(CC_ERR_INVALID,
-                         "yuv420sp: 4:2:0 needs even dims (got %dx%d)", w, h);
-  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12)
-    return cc::set_error(CC_ERR_INVALID,
-                         "yuv420sp: bit_depth must be 8, 10 or 12 (got %d)",
-                         bit_depth);
-  if (matrix < 0 || matrix > 2)
-    return cc::set_error(CC_ERR_INVALID, "yuv420sp: matrix must be 0 (bt601), "
-                         "1 (bt709) or 2 (bt2020) (got %d)", matrix);
-  if (full_range != 0 && full_range != 1)
-    return cc::set_error(CC_ERR_INVALID,
-                         "yuv420sp: full_range must be 0 or 1 (got %d)",
-                         full_range);
-  const size_t bps = bit_depth == 8 ? 1 : 2;
-  if (pitch < (size_t)w * bps)
-    return cc::set_error(CC_ERR_INVALID, "yuv420sp: pitch %zu < row bytes %zu",
-                         pitch, (size_t)w * bps);
-  if (bps == 2 && ((pitch | (size_t)y | (size_t)uv) & 1))
-    return cc::set_error(CC_ERR_INVALID, "yuv420sp: 16-bit planes need an "
-                         "even pitch and 2-byte-aligned pointers");
-  return CC_OK;
+  return yuv420sp_launch("nv12_to_rgb_resize", y, uv, n, src_h, src_w, pitch,
+                         8, 0, 0, out_rgb, true, out_h, out_w, stream);
 }
 
 int cc_yuv420sp_to_rgb(const void* y, const void* uv, int n, int h, int w,
                        size_t pitch_bytes, int bit_depth, int matrix,
                        int full_range, void* out_rgb, uint64_t stream) {
-  int rc = yuv420sp_check(y, uv, out_rgb, n, h, w, pitch_bytes, bit_depth,
-                          matrix, full_range);
-  if (rc != CC_OK) return rc;
-  const YuvCoef k = kYuvCoef[matrix][full_range ? 1 + (bit_depth - 8) / 2 : 0];
-  const int shift = bit_depth == 8 ? 0 : 16 - bit_depth;
-  const float scale = 1.0f / (float)(1 << (bit_depth - 8));
-  const unsigned char* yp = (const unsigned char*)y;
-  const unsigned char* uvp = (const unsigned char*)uv;
-  unsigned char* op = (unsigned char*)out_rgb;
-  // 16-byte-aligned planes and pitch: 8-pixel runs go through the vector
-  // kernel and only the w % 8 row tails through the scalar one
-  const bool aligned = (((size_t)y | (size_t)uv | pitch_bytes) & 15) == 0;
-  const int x_vec = aligned ? (w / 8) * 8 : 0;
-  dim3 block(256);
-  if (x_vec > 0) {
-    long runs = (long)n * h * (w / 8);
-    dim3 grid((unsigned)((runs + 255) / 256));
-    if (bit_depth == 8)
-      CC_LAUNCH("yuv420sp_to_rgb", grid, block, stream,
-                k_yuv420sp_to_rgb_v8<uint8_t>, yp, uvp, n, h, w, pitch_bytes,
-                shift, scale, k, op);
-    else
-      CC_LAUNCH("yuv420sp_to_rgb", grid, block, stream,
-                k_yuv420sp_to_rgb_v8<uint16_t>, yp, uvp, n, h, w, pitch_bytes,
-                shift, scale, k, op);
-  }
-  if (x_vec < w) {
-    long total = (long)n * h * (w - x_vec);
-    dim3 grid((unsigned)((total + 255) / 256));
-    if (bit_depth == 8)
-      CC_LAUNCH("yuv420sp_to_rgb", grid, block, stream,
-                k_yuv420sp_to_rgb_px<uint8_t>, yp, uvp, n, h, w, x_vec,
-                pitch_bytes, shift, scale, k, op);
-    else
-      CC_LAUNCH("yuv420sp_to_rgb", grid, block, stream,
-                k_yuv420sp_to_rgb_px<uint16_t>, yp, uvp, n, h, w, x_vec,
-                pitch_bytes, shift, scale, k, op);
-  }
-  return CC_OK;
+  return yuv420sp_launch("yuv420sp_to_rgb", y, uv, n, h, w, pitch_bytes,
+                         bit_depth, matrix, full_range, out_rgb, false, 0, 0,
+                         stream);
 }
 
 int cc_yuv420sp_to_rgb_resize(const void* y, const void* uv, int n, int src_h,
                               int src_w, size_t pitch_bytes, int bit_depth,
                               int matrix, int full_range, void* out_rgb,
                               int out_h, int out_w, uint64_t stream) {
-  int rc = yuv420sp_check(y, uv, out_rgb, n, src_h, src_w, pitch_bytes,
-                          bit_depth, matrix, full_range);
-  if (rc != CC_OK) return rc;
-  if (out_h <= 0 || out_w <= 0)
-    return cc::set_error(CC_ERR_INVALID,
-                         "yuv420sp: non-positive output size %dx%d", out_w,
-                         out_h);
-  const YuvCoef k = kYuvCoef[matrix][full_range ? 1 + (bit_depth - 8) / 2 : 0];
-  const int shift = bit_depth == 8 ? 0 : 16 - bit_depth;
-  const float scale = 1.0f / (float)(1 << (bit_depth - 8));
-  long total = (long)n * out_h * out_w;
-  dim3 block(256), grid((unsigned)((total + 255) / 256));
-  if (bit_depth == 8)
-    CC_LAUNCH("yuv420sp_to_rgb_resize", grid, block, stream,
-              k_yuv420sp_to_rgb_resize<uint8_t>, (const unsigned char*)y,
-              (const unsigned char*)uv, n, src_h, src_w, pitch_bytes, shift,
-              scale, k, (unsigned char*)out_rgb, out_h, out_w);
-  else
-    CC_LAUNCH("yuv420sp_to_rgb_resize", grid, block, stream,
-              k_yuv420sp_to_rgb_resize<uint16_t>, (const unsigned char*)y,
-              (const unsigned char*)uv, n, src_h, src_w, pitch_bytes, shift,
-              scale, k, (unsigned char*)out_rgb, out_h, out_w);
-  return CC_OK;
+  return yuv420sp_launch("yuv420sp_to_rgb_resize", y, uv, n, src_h, src_w,
+                         pitch_bytes, bit_depth, matrix, full_range, out_rgb,
+                         true, out_h, out_w, stream);
 }
 
 int cc_resize_bilinear_u8(const void* in, int n, int src_h, int src_w,
@@ -887,10 +789,11 @@ int cc_resize_bilinear_u8(const void* in, int n, int src_h, int src_w,
   if (!in || !out || n <= 0) return cc::set_error(CC_ERR_INVALID, "bad args");
   long total = (long)n * dst_h * dst_w;
   dim3 block(256), grid((total + 255) / 256);
-  CC_LAUNCH("resize_bilinear_u8", grid, block, stream, k_resize_bilinear_u8,
-            (const unsigned char*)in, n, src_h, src_w, (unsigned char*)out,
-            dst_h, dst_w);
-  return CC_OK;
+  return cc::timed_launch("resize_bilinear_u8", stream, [&] {
+    hipLaunchKernelGGL(k_resize_bilinear_u8, grid, block, 0,
+                       (hipStream_t)stream, (const unsigned char*)in, n, src_h,
+                       src_w, (unsigned char*)out, dst_h, dst_w);
+  });
 }
 
 int cc_resize_bicubic_u8(const void* in, int n, int src_h, int src_w, void* out,
@@ -898,10 +801,11 @@ int cc_resize_bicubic_u8(const void* in, int n, int src_h, int src_w, void* out,
   if (!in || !out || n <= 0) return cc::set_error(CC_ERR_INVALID, "bad args");
   long total = (long)n * dst_h * dst_w;
   dim3 block(256), grid((total + 255) / 256);
-  CC_LAUNCH("resize_bicubic_u8", grid, block, stream, k_resize_bicubic_u8,
-            (const unsigned char*)in, n, src_h, src_w, (unsigned char*)out,
-            dst_h, dst_w);
-  return CC_OK;
+  return cc::timed_launch("resize_bicubic_u8", stream, [&] {
+    hipLaunchKernelGGL(k_resize_bicubic_u8, grid, block, 0,
+                       (hipStream_t)stream, (const unsigned char*)in, n, src_h,
+                       src_w, (unsigned char*)out, dst_h, dst_w);
+  });
 }
 
 int cc_clip_preprocess(const void* in, int n, int h, int w, const float mean[3],
@@ -909,23 +813,24 @@ int cc_clip_preprocess(const void* in, int n, int h, int w, const float mean[3],
                        uint64_t stream) {
   if (!in || !out || !mean || !stdev || n <= 0)
     return cc::set_error(CC_ERR_INVALID, "bad args");
+  if (out_dtype != 0 && out_dtype != 1)
+    return cc::set_error(CC_ERR_INVALID, "out_dtype must be 0(f32)|1(bf16)");
   long total = (long)n * h * w;
   dim3 block(256), grid((total + 255) / 256);
-  if (out_dtype == 0) {
-    CC_LAUNCH("clip_preprocess", grid, block, stream, k_clip_preprocess_f32,
-              (const unsigned char*)in, n, h, w, mean[0], mean[1], mean[2],
-              stdev[0], stdev[1], stdev[2], (float*)out);
-  } else if (out_dtype == 1) {
-    dim3 gridq(((total + 3) / 4 + 255) / 256);  // 4 pixels per thread
-    CC_LAUNCH("clip_preprocess", gridq, block, stream, k_clip_preprocess_bf16,
-              (const unsigned char*)in, n, h, w, mean[0], mean[1], mean[2],
-              stdev[0], stdev[1], stdev[2], (unsigned short*)out);
-  } else {
-    return cc::set_error(CC_ERR_INVALID, "out_dtype must be 0(f32)|1(bf16)");
-  }
-  return CC_OK;
+  dim3 gridq(((total + 3) / 4 + 255) / 256);  // bf16: 4 pixels per thread
+  return cc::timed_launch("clip_preprocess", stream, [&] {
+    if (out_dtype == 0)
+      hipLaunchKernelGGL(k_clip_preprocess_f32, grid, block, 0,
+                         (hipStream_t)stream, (const unsigned char*)in, n, h,
+                         w, mean[0], mean[1], mean[2], stdev[0], stdev[1],
+                         stdev[2], (float*)out);
+    else
+      hipLaunchKernelGGL(k_clip_preprocess_bf16, gridq, block, 0,
+                         (hipStream_t)stream, (const unsigned char*)in, n, h,
+                         w, mean[0], mean[1], mean[2], stdev[0], stdev[1],
+                         stdev[2], (unsigned short*)out);
+  });
 }
-
 
 int cc_clip_preprocess_patches(const void* in, int n, int h, int w, int patch,
                                int kpad, const float mean[3],
@@ -937,28 +842,25 @@ int cc_clip_preprocess_patches(const void* in, int n, int h, int w, int patch,
       kpad < 3 * patch * patch)
     return cc::set_error(CC_ERR_UNSUPPORTED,
                          "need h,w %% patch == 0 and kpad %% 64 == 0, >= 3*P*P");
-  long rows = (long)n * (h / patch) * (w / patch);
-  long quads = rows * (kpad / 4);
-  dim3 block(256), grid((quads + 255) / 256);
+  const long rows = (long)n * (h / patch) * (w / patch);
   const long pp2 = (long)patch * patch;
-  static const int pp16_env = [] {
-    const char* e = getenv("CC_PP16");
-    return e ? atoi(e) : 1;
-  }();
-  if (pp16_env && patch % 16 == 0 && (3 * w) % 16 == 0 && kpad == 3 * pp2) {
-    const long rows = (long)n * (h / patch) * (w / patch);
-    const long total16 = rows * (kpad / 16);
-    dim3 grid16((unsigned)((total16 + 255) / 256));
-    CC_LAUNCH("clip_preprocess", grid16, block, stream,
-              k_clip_preprocess_patches16, (const unsigned char*)in, n, h, w,
-              patch, kpad, mean[0], mean[1], mean[2], stdev[0], stdev[1],
-              stdev[2], (unsigned short*)out);
-    return CC_OK;
-  }
-  CC_LAUNCH("clip_preprocess", grid, block, stream, k_clip_preprocess_patches,
-            (const unsigned char*)in, n, h, w, patch, kpad, mean[0], mean[1],
-            mean[2], stdev[0], stdev[1], stdev[2], (unsigned short*)out);
-  return CC_OK;
+  // 16 columns per thread where the kernel's alignment conditions hold,
+  // 4 everywhere else
+  const bool cols16 = patch % 16 == 0 && (3 * w) % 16 == 0 && kpad == 3 * pp2;
+  const long threads = rows * (kpad / (cols16 ? 16 : 4));
+  dim3 block(256), grid((unsigned)((threads + 255) / 256));
+  return cc::timed_launch("clip_preprocess", stream, [&] {
+    if (cols16)
+      hipLaunchKernelGGL(k_clip_preprocess_patches16, grid, block, 0,
+                         (hipStream_t)stream, (const unsigned char*)in, n, h,
+                         w, patch, kpad, mean[0], mean[1], mean[2], stdev[0],
+                         stdev[1], stdev[2], (unsigned short*)out);
+    else
+      hipLaunchKernelGGL(k_clip_preprocess_patches, grid, block, 0,
+                         (hipStream_t)stream, (const unsigned char*)in, n, h,
+                         w, patch, kpad, mean[0], mean[1], mean[2], stdev[0],
+                         stdev[1], stdev[2], (unsigned short*)out);
+  });
 }
 
 int cc_gather_frames_u8(const void* frames, int n_in, size_t frame_bytes,
@@ -984,21 +886,16 @@ int cc_gather_frames_u8(const void* frames, int n_in, size_t frame_bytes,
                                   (hipStream_t)stream));
   long total = (long)total_out * (long)frame_bytes;
   dim3 block(256), grid((total + 255) / 256);
-  hipEvent_t _evs[2];
-  bool _timed;
-  launch_timed("gather_frames_u8", stream, _evs, &_timed);
-  hipLaunchKernelGGL(k_gather_frames_u8, grid, block, 0, (hipStream_t)stream,
-                     (const unsigned char*)frames, frame_bytes, d_src,
-                     total_out, (unsigned char*)out);
-  hipError_t e = hipGetLastError();
-  finish_timed("gather_frames_u8", stream, _evs, _timed);
+  int rc = cc::timed_launch("gather_frames_u8", stream, [&] {
+    hipLaunchKernelGGL(k_gather_frames_u8, grid, block, 0, (hipStream_t)stream,
+                       (const unsigned char*)frames, frame_bytes, d_src,
+                       total_out, (unsigned char*)out);
+  });
   // free after the kernel: synchronize the stream (gather is not on the
   // steady-state hot loop; clip selection happens once per clip batch)
   hipStreamSynchronize((hipStream_t)stream);
   hipFree(d_src);
-  if (e != hipSuccess)
-    return cc::set_error(CC_ERR_HIP, "gather launch: %s", hipGetErrorString(e));
-  return CC_OK;
+  return rc;
 }
 
 }  // extern "C"

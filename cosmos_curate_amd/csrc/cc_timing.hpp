@@ -32,6 +32,22 @@ inline void timed_end(const char* name, uint64_t stream, hipEvent_t ev0,
   ts.pending.push_back({name, (void*)ev0, (void*)ev1});
 }
 
+// one kernel launch, timed when timing is on.  `enqueue` issues exactly
+// one hipLaunchKernelGGL (it may pick the instantiation with if/switch).
+// Every timed_begin that succeeds is ended, launch error or not, so no
+// path leaks the event pair.  Returns CC_OK or CC_ERR_HIP.
+template <typename Enqueue>
+inline int timed_launch(const char* name, uint64_t stream, Enqueue&& enqueue) {
+  hipEvent_t ev0, ev1;
+  const bool timed = timed_begin(stream, &ev0, &ev1);
+  enqueue();
+  const hipError_t e = hipGetLastError();
+  if (timed) timed_end(name, stream, ev0, ev1);
+  if (e != hipSuccess)
+    return set_error(CC_ERR_HIP, "%s launch: %s", name, hipGetErrorString(e));
+  return CC_OK;
+}
+
 // drain pending pairs into the per-kernel totals (synchronizes on the
 // recorded events; call from cc_timing_report / cc_timing_reset).
 inline void timed_drain() {

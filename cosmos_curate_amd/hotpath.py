@@ -182,18 +182,13 @@ def yuv_to_rgb_resize(
 ) -> None:
     """Fused 4:2:0 semi-planar -> RGB + bilinear resize on device pointers.
 
-    8-bit BT.601 limited range stays on cc_nv12_to_rgb_resize (the path and
-    the bits every 8-bit consumer has always had); every other combination
-    runs cc_yuv420sp_to_rgb_resize.  No fallback: a failing call raises.
+    Always cc_yuv420sp_to_rgb_resize: the library's one YUV launcher picks
+    the kernel, and at (8, bt601, limited) that is the kernel and the bits
+    of cc_nv12_to_rgb_resize.  No fallback: a failing call raises.
     """
-    lib = load()
-    if bit_depth == 8 and matrix == 0 and not full_range:
-        check(lib.cc_nv12_to_rgb_resize(
-            y, uv, n, src_h, src_w, pitch_bytes, out_rgb, out_h, out_w, stream))
-    else:
-        check(lib.cc_yuv420sp_to_rgb_resize(
-            y, uv, n, src_h, src_w, pitch_bytes, bit_depth, matrix,
-            int(bool(full_range)), out_rgb, out_h, out_w, stream))
+    check(load().cc_yuv420sp_to_rgb_resize(
+        y, uv, n, src_h, src_w, pitch_bytes, bit_depth, matrix,
+        int(bool(full_range)), out_rgb, out_h, out_w, stream))
 
 
 def estimate_motion(

@@ -12,8 +12,8 @@ MI355X path:
     sample_closest on PTS                            [host, §8 row a2]
     NV12 surfaces -> HBM (rocDecode | raw upload)    [device]
     fused YUV->RGB + bilinear resize kernel          [device, §2b rows 3-5]
-      (8-bit BT.601: cc_nv12_to_rgb_resize; 10/12-bit P016 or another
-       colour standard: cc_yuv420sp_to_rgb_resize)
+      (cc_yuv420sp_to_rgb_resize for every depth and colour standard;
+       8-bit BT.601 limited gives the bits of cc_nv12_to_rgb_resize)
     duplicate-count broadcast (cc_gather_frames_u8)  [device]
 
 Output frames live on DEVICE as torch uint8 NHWC tensors keyed by

@@ -139,7 +139,11 @@ void cc_decode_destroy(cc_decode_t* s);
 /* NV12 (Y plane + interleaved UV half-res plane, same pitch) ->
  * RGB888 NHWC at (out_h,out_w) via bilinear taps in converted-RGB space
  * (each tap converted BT.601 limited-range and rounded to u8 first —
- * bit-identical to convert-then-resize, fused to skip the intermediate). */
+ * bit-identical to convert-then-resize, fused to skip the intermediate).
+ * This and cc_nv12_to_rgb are cc_yuv420sp_to_rgb[_resize] at (8, 0, 0):
+ * one launcher, the same kernels; only the timing names differ
+ * ("nv12_to_rgb_resize", "nv12_to_rgb").  CC_ERR_INVALID on null pointers,
+ * non-positive sizes, odd h/w or pitch < w. */
 int cc_nv12_to_rgb_resize(const void* y, const void* uv, int n,
                           int src_h, int src_w, size_t pitch,
                           void* out_rgb, int out_h, int out_w,
@@ -158,7 +162,7 @@ int cc_nv12_to_rgb(const void* y, const void* uv, int n,
  *   full_range  0 = limited (16..235 / 16..240 scaled), 1 = full
  * Frame f's Y plane starts at y + f*pitch_bytes*h, its UV plane at
  * uv + f*pitch_bytes*(h/2).  f32 arithmetic, bit-exact vs tests/yuv_ref.py;
- * (8, 0, 0) is bit-identical to cc_nv12_to_rgb.  Planes and pitch that
+ * (8, 0, 0) is what cc_nv12_to_rgb runs.  Planes and pitch that
  * are 16-byte aligned take the vectorised path (8 pixels per lane);
  * anything else, and w % 8 row tails, a scalar one.  CC_ERR_INVALID on odd
  * h/w, out-of-set bit_depth/matrix/full_range, pitch_bytes <
@@ -170,8 +174,8 @@ int cc_yuv420sp_to_rgb(const void* y, const void* uv, int n, int h, int w,
 /* The same conversion fused with the bilinear resize
  * (cvcuda.resize_into(LINEAR), nvcodec_utils.py:189-194): each of the four
  * taps is converted and rounded to u8 first — bit-identical to
- * cc_yuv420sp_to_rgb followed by cc_resize_bilinear_u8, and (8, 0, 0) is
- * bit-identical to cc_nv12_to_rgb_resize. */
+ * cc_yuv420sp_to_rgb followed by cc_resize_bilinear_u8; (8, 0, 0) is what
+ * cc_nv12_to_rgb_resize runs. */
 int cc_yuv420sp_to_rgb_resize(const void* y, const void* uv, int n,
                               int src_h, int src_w, size_t pitch_bytes,
                               int bit_depth, int matrix, int full_range,

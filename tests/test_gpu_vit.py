@@ -281,6 +281,61 @@ def test_embed_assemble_ln_vs_torch(lib):
     torch.testing.assert_close(out.float(), want, rtol=2e-2, atol=2e-2)
 
 
+def test_ln_entries_reject_h_without_instantiation_while_timing(lib):
+    """H = 1280 is a multiple of 256 but no kernel is instantiated for it:
+    both entries refuse it before any timing event exists, so with timing
+    on nothing is left pending and a following valid call counts once."""
+    import ctypes
+
+    torch.manual_seed(29)
+    eps = ctypes.c_float(1e-5)
+    stream = torch.cuda.current_stream().cuda_stream
+    n, tokens = 2, 2  # 4 rows
+
+    def buffers(H):
+        return dict(
+            x=torch.randn(n * tokens, H).to(torch.bfloat16).cuda(),
+            tok=torch.randn(n * (tokens - 1), H).to(torch.bfloat16).cuda(),
+            cls=torch.randn(H).float().cuda(), pos=torch.randn(tokens, H).float().cuda(),
+            w=torch.randn(H).float().cuda(), b=torch.randn(H).float().cuda(),
+            out=torch.empty(n * tokens, H, dtype=torch.bfloat16, device="cuda"))
+
+    def layernorm(t, H):
+        return lib.cc_layernorm_bf16(t["x"].data_ptr(), t["w"].data_ptr(),
+                                     t["b"].data_ptr(), t["out"].data_ptr(),
+                                     n * tokens, H, eps, stream)
+
+    def embed(t, H):
+        return lib.cc_embed_assemble_ln(
+            t["tok"].data_ptr(), t["cls"].data_ptr(), t["pos"].data_ptr(),
+            t["w"].data_ptr(), t["b"].data_ptr(), t["out"].data_ptr(), n, tokens, H,
+            eps, stream)
+
+    bad, good = buffers(1280), buffers(256)
+    hotpath.timing_enable(True)
+    try:
+        for call in (layernorm, embed):
+            assert call(bad, 1280) == -6, call.__name__  # CC_ERR_UNSUPPORTED
+            assert lib.cc_last_error().decode(), call.__name__
+        hotpath.check(layernorm(good, 256))
+        torch.cuda.synchronize()
+        want = torch.nn.functional.layer_norm(good["x"].float(), (256,), good["w"],
+                                              good["b"], eps=1e-5)
+        torch.testing.assert_close(good["out"].float(), want, rtol=2e-2, atol=2e-2)
+        hotpath.check(embed(good, 256))
+        torch.cuda.synchronize()
+        h = torch.cat([good["cls"].to(torch.bfloat16).expand(n, 1, 256),
+                       good["tok"].reshape(n, tokens - 1, 256)], dim=1)
+        h = (h.float() + good["pos"].unsqueeze(0)).to(torch.bfloat16)
+        want = torch.nn.functional.layer_norm(
+            h.float(), (256,), good["w"], good["b"], eps=1e-5).reshape(n * tokens, 256)
+        torch.testing.assert_close(good["out"].float(), want, rtol=2e-2, atol=2e-2)
+        assert hotpath.timing_report("layernorm_bf16")[1] == 1
+        assert hotpath.timing_report("embed_assemble_ln")[1] == 1
+    finally:
+        hotpath.timing_enable(False)
+
+
 def test_attn_mid_vs_sdpa(lib):
     """cc_attn_mid (seq=257, L/14 shape) == torch sdpa on the same QKV."""
     import ctypes

@@ -130,6 +130,9 @@ def test_extremes(lib, depth):
 # ---- 3. cross-checks against the existing 8-bit kernels ----------------------
 
 def test_depth8_bt601_equals_nv12_kernels(lib):
+    """The cc_nv12_* entries are the yuv420sp launcher at (8, bt601, limited),
+    so entry-point equality compares a kernel with itself; the independent
+    truth is oracle/color.py, on the same pitched planes."""
     rng = np.random.default_rng(5)
     for n, h, w, pitch16 in SHAPES:
         pitch = pitch16 // 2
@@ -140,6 +143,9 @@ def test_depth8_bt601_equals_nv12_kernels(lib):
                                          pitch, old.data_ptr(), 0))
         new = convert(lib, y, uv, pitch, 8, 0, 0)
         assert torch.equal(old, new), (n, h, w)
+        want = np.stack([ocolor.nv12_to_rgb(y[i], uv[i].reshape(h // 2, w // 2, 2))
+                         for i in range(n)])
+        np.testing.assert_array_equal(old.cpu().numpy(), want, err_msg=str((n, h, w)))
         for oh, ow in ((7, 9), (2 * h + 1, 2 * w - 3)):
             old_r = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device="cuda")
             hotpath.check(lib.cc_nv12_to_rgb_resize(
@@ -147,6 +153,63 @@ def test_depth8_bt601_equals_nv12_kernels(lib):
                 oh, ow, 0))
             new_r = convert_resize(lib, y, uv, pitch, 8, 0, 0, oh, ow)
             assert torch.equal(old_r, new_r), (n, h, w, oh, ow)
+            want_r = np.stack([ocolor.resize_bilinear_u8(f, oh, ow) for f in want])
+            np.testing.assert_array_equal(old_r.cpu().numpy(), want_r,
+                                          err_msg=str((n, h, w, oh, ow)))
+
+
+@pytest.mark.parametrize("depth", (8, 10))
+def test_misaligned_base_takes_the_scalar_kernel(lib, depth):
+    """Planes 8- but not 16-byte aligned, rows a multiple of 8 pixels at a
+    16-byte-multiple pitch: only the base-alignment test keeps the call off
+    the vector kernel's 16-byte loads.  Depth 8 goes through cc_nv12_to_rgb,
+    which depends on that dispatch since it shares the launcher."""
+    n, h, w = 1, 4, 16
+    pitch = 16 if depth == 8 else 32
+    rng = np.random.default_rng(8 + depth)
+    y, uv = rand_planes(rng, n, h, w, depth)
+
+    def carve(plane):  # the plane's bytes at offset 8 of a 0xA5-filled buffer
+        raw = torch.from_numpy(np.ascontiguousarray(plane).view(np.uint8).reshape(-1))
+        buf = torch.full((raw.numel() + 24,), 0xA5, dtype=torch.uint8, device="cuda")
+        buf[8:8 + raw.numel()] = raw.cuda()
+        assert buf.data_ptr() % 16 == 0
+        return buf, buf.data_ptr() + 8
+
+    ybuf, yp = carve(y)
+    uvbuf, uvp = carve(uv)
+    nbytes, guard = n * h * w * 3, 64
+    out = torch.full((nbytes + guard,), 0x5A, dtype=torch.uint8, device="cuda")
+    if depth == 8:
+        hotpath.check(lib.cc_nv12_to_rgb(yp, uvp, n, h, w, pitch, out.data_ptr(), 0))
+    else:
+        hotpath.check(lib.cc_yuv420sp_to_rgb(yp, uvp, n, h, w, pitch, depth, 0, 0,
+                                             out.data_ptr(), 0))
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    want = yuv_ref.yuv420sp_to_rgb_batch(y, uv, depth, 0, 0)
+    np.testing.assert_array_equal(got[:nbytes].reshape(n, h, w, 3), want)
+    assert (got[nbytes:] == 0x5A).all()  # guard bytes untouched
+
+
+def test_nv12_entries_keep_their_timing_names(lib):
+    n, h, w, _ = SHAPES[0]  # 6x10: the scalar kernel alone
+    y, uv = rand_planes(np.random.default_rng(9), n, h, w, 8)
+    yd, uvd = _dev(y), _dev(uv)
+    full = torch.empty((n, h, w, 3), dtype=torch.uint8, device="cuda")
+    small = torch.empty((n, 3, 5, 3), dtype=torch.uint8, device="cuda")
+    hotpath.timing_enable(True)
+    try:
+        hotpath.check(lib.cc_nv12_to_rgb_resize(
+            yd.data_ptr(), uvd.data_ptr(), n, h, w, w, small.data_ptr(), 3, 5, 0))
+        hotpath.check(lib.cc_nv12_to_rgb(yd.data_ptr(), uvd.data_ptr(), n, h, w, w,
+                                         full.data_ptr(), 0))
+        torch.cuda.synchronize()
+        assert hotpath.timing_report("nv12_to_rgb_resize")[1] == 1
+        assert hotpath.timing_report("nv12_to_rgb")[1] >= 1  # body and/or row tail
+        assert hotpath.timing_report("yuv420sp_to_rgb")[1] == 0
+    finally:
+        hotpath.timing_enable(False)
 
 
 @pytest.mark.parametrize("depth", (10, 12))

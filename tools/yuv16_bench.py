@@ -1,13 +1,23 @@
-"""Time cc_yuv420sp_to_rgb (10-bit P016) against cc_nv12_to_rgb (8-bit) on
-one MI355X, at the same geometry, alternating the two in one process.
+"""Time the YUV->RGB kernel family on one MI355X, the legs alternating in one
+process: cc_nv12_to_rgb (8-bit) and cc_yuv420sp_to_rgb (10-bit P016) at the
+same full-resolution geometry — one launcher, the u8 and u16 instantiations
+of the same kernels — and cc_nv12_to_rgb_resize at bench.py's own geometry
+(its SRC_H x SRC_W source at pitch SRC_W, 224x224 output, 21 frames x 8
+clips): the first kernel of bench.py's timed region.
 
     python tools/yuv16_bench.py [--frames 8 --height 2160 --width 3840
                                  --launches 30 --warmup 5] [--out LOG]
+                                [--legs all|full|resize]
 
 Per-launch device time from HIP events around each launch on the current
 stream; prints (and with --out also writes) medians, spread, the achieved
 GB/s from the bytes the algorithm must move (Y + UV in, RGB out), and that
-rate as a fraction of the 6.29 TB/s measured copy rate.
+rate as a fraction of the 6.29 TB/s measured copy rate.  The
+frame geometry options apply to the two full-resolution legs only.
+--legs resize times the fused kernel alone: what ran just before a launch
+moves its time (the unchanged 10-bit kernel differs by ~5 % between a
+process whose 8-bit leg is slow and one whose 8-bit leg is fast), so a
+before/after comparison of one leg runs that leg by itself on both sides.
 Needs a GPU; there is no fallback.
 """
 
@@ -22,6 +32,7 @@ import torch
 
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
 
+from bench import FRAMES_PER_CLIP, RES, SRC_H, SRC_W  # noqa: E402
 from cosmos_curate_amd import hotpath  # noqa: E402
 
 COPY_RATE_GBS = 6290.0  # measured float4 copy rate, MI355X
@@ -35,6 +46,7 @@ def main() -> None:
     ap.add_argument("--launches", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--legs", choices=("all", "full", "resize"), default="all")
     args = ap.parse_args()
     n, h, w = args.frames, args.height, args.width
 
@@ -49,6 +61,12 @@ def main() -> None:
                          generator=g)
     out8 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
     out16 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    rn = FRAMES_PER_CLIP * 8
+    ry = torch.randint(0, 256, (rn, SRC_H, SRC_W), dtype=torch.uint8, device=dev,
+                       generator=g)
+    ruv = torch.randint(0, 256, (rn, SRC_H // 2, SRC_W), dtype=torch.uint8, device=dev,
+                        generator=g)
+    rout = torch.empty((rn, RES, RES, 3), dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
 
     def run_nv12() -> None:
@@ -60,11 +78,22 @@ def main() -> None:
             y16.data_ptr(), uv16.data_ptr(), n, h, w, 2 * w, 10, 1, 0,
             out16.data_ptr(), stream))
 
-    legs = {"nv12_to_rgb (8-bit, bt601)": (run_nv12, 4.5),
-            "yuv420sp_to_rgb (10-bit, bt709)": (run_p010, 6.0)}
+    def run_resize() -> None:
+        hotpath.check(lib.cc_nv12_to_rgb_resize(
+            ry.data_ptr(), ruv.data_ptr(), rn, SRC_H, SRC_W, SRC_W, rout.data_ptr(),
+            RES, RES, stream))
+
+    # name -> (launch, bytes the algorithm must move per launch)
+    legs = {"nv12_to_rgb (8-bit, bt601)": (run_nv12, n * h * w * 4.5),
+            "yuv420sp_to_rgb (10-bit, bt709)": (run_p010, n * h * w * 6.0),
+            f"nv12_to_rgb_resize ({rn} x {SRC_H}x{SRC_W} -> {RES}x{RES})":
+                (run_resize, rn * (SRC_H * SRC_W * 1.5 + RES * RES * 3))}
+    if args.legs != "all":
+        legs = {k: v for k, v in legs.items()
+                if ("resize" in k) == (args.legs == "resize")}
     times: dict[str, list[float]] = {k: [] for k in legs}
     for it in range(args.warmup + args.launches):
-        for name, (fn, _) in legs.items():  # alternate the two legs
+        for name, (fn, _) in legs.items():  # alternate the legs
             e0 = torch.cuda.Event(enable_timing=True)
             e1 = torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -74,17 +103,17 @@ def main() -> None:
             if it >= args.warmup:
                 times[name].append(e0.elapsed_time(e1))
 
-    lines = [f"geometry: {n} frames of {h}x{w}; {args.launches} launches each "
+    lines = [f"full-resolution legs: {n} frames of {h}x{w}; {args.launches} launches each "
              f"after {args.warmup} warm-up, alternating; device "
              f"{torch.cuda.get_device_name(0)}"]
-    for name, (_, bytes_per_px) in legs.items():
+    for name, (_, nbytes) in legs.items():
         t = np.array(times[name])
         med = float(np.median(t))
-        gbs = n * h * w * bytes_per_px / (med * 1e-3) / 1e9
+        gbs = nbytes / (med * 1e-3) / 1e9
         lines.append(
             f"{name}: median {med:.4f} ms  min {t.min():.4f}  max {t.max():.4f}  "
             f"p10 {np.percentile(t, 10):.4f}  p90 {np.percentile(t, 90):.4f}  | "
-            f"{bytes_per_px} B/px -> {gbs:.0f} GB/s = {gbs / COPY_RATE_GBS:.3f} of "
+            f"{nbytes / 1e6:.1f} MB -> {gbs:.0f} GB/s = {gbs / COPY_RATE_GBS:.3f} of "
             f"the {COPY_RATE_GBS / 1000:.2f} TB/s copy rate")
     text = "\n".join(lines)
     print(text)
