@@ -2,15 +2,17 @@
 // by sequence length, all reading Q/K/V straight out of the fused-QKV
 // GEMM output ([n*seq, 3*H] rows tokens) and writing O contiguous
 // [n*seq, H] (the out-projection GEMM's input layout), replacing
-// torch-rocm sdpa (~94 TF/s) + the qkv permute copies:
-//   k_attn_small  seq <= 64   (ViT-B/32's 50): everything LDS-resident,
-//                 4 WG... 2 WG/CU — see its note on the direct-global
-//                 variant that measured slower here;
-//   k_attn_mid    64 < seq <= 288 (ViT-L/14's 257, SigLIP-L16-256's
-//                 256): Q/K fragments direct from global (16B-contiguous
-//                 rows), LDS only V^T + P -> 2 WG/CU;
-//   k_attn_flash  seq > 288 (SigLIP-384-class): K/V streamed in 64-row
-//                 tiles with online softmax, O rescaled flash-style.
+// torch-rocm sdpa (~94 TF/s) + the qkv permute copies.  Which rung a
+// sequence length runs, and its grid, is decided by cc::attn_plan
+// (cc_attn_plan.hpp) and nowhere else; cc_attn executes that plan:
+//   k_attn_small  (ViT-B/32's 50): everything LDS-resident, 2 WG/CU —
+//                 see its note on the direct-global variant that
+//                 measured slower here;
+//   k_attn_mid    (ViT-L/14's 257, SigLIP-L16-256's 256): Q/K fragments
+//                 direct from global (16B-contiguous rows), LDS only
+//                 V^T + P -> 2 WG/CU;
+//   k_attn_flash  (SigLIP-384-class): K/V streamed in 64-row tiles with
+//                 online softmax, O rescaled flash-style.
 // Plus k_attn_cls (any seq): one query row per (frame, head) for the
 // last layer of a CLS-pooled tower — separate q, strided K/V, O [n, H].
 //
@@ -23,6 +25,7 @@
 
 #include <vector>
 
+#include "cc_attn_plan.hpp"
 #include "cc_common.hpp"
 #include "cc_timing.hpp"
 
@@ -31,8 +34,8 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-constexpr int SMAX = 64;   // padded sequence tile
-constexpr int HD = 64;     // head dim
+constexpr int SMAX = cc::ATTN_SMALL_MAX;  // padded sequence tile
+constexpr int HD = cc::ATTN_HD;           // head dim
 constexpr int LD = 72;     // LDS row stride (pad 8 elements vs 64 banks)
 
 // NOTE: the direct-global Q/K variant (4 WG/CU) was tried here too and
@@ -182,7 +185,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_small(
 }
 
 
-// ---- mid-sequence variant (64 < seq <= 288): ViT-L/14's seq=257 ----
+// ---- mid-sequence variant: ViT-L/14's seq=257 ----
 // One workgroup per (frame, head), Q in 64-row tiles.  Q and K
 // fragments are 16-byte contiguous in the fused-QKV layout, so they
 // load STRAIGHT from global/L2 (no LDS staging) — only V^T (transposed
@@ -190,7 +193,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_small(
 // doubles the waves/SIMD vs the LDS-everything form (measured 621 us
 // -> see profiles/r01_attn_mid2; the LDS-everything form capped at
 // ~204 TF with 1 wave/SIMD).
-constexpr int SMID = 288;       // padded sequence (18 x 16-col frags)
+constexpr int SMID = cc::ATTN_MID_MAX;  // padded sequence (18 x 16-col frags)
 constexpr int LDM = SMID + 8;   // LDS s-stride for Vt / P rows
 
 __global__ __launch_bounds__(256, 2) void k_attn_mid(
@@ -340,8 +343,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_mid(
 }
 
 
-// ---- flash variant (seq > 288): K/V streamed in 64-row tiles with
-// online softmax ----
+// ---- flash variant (past the mid rung): K/V streamed in 64-row tiles
+// with online softmax ----
 // One workgroup per (frame, head, q-tile of 64 rows); Q and K fragments
 // load straight from global (16B-contiguous in the fused-QKV layout,
 // same trick as k_attn_mid); per KV-tile, V^T and the probability tile
@@ -649,52 +652,76 @@ extern "C" int cc_attn_cls(const void* q, const void* k, const void* v,
   });
 }
 
+namespace {
+
+using AttnKernel = void (*)(const __bf16*, __bf16*, long, int, int, int,
+                            float);
+struct AttnRung {
+  const char* label;  // timing name
+  AttnKernel kernel;
+};
+constexpr AttnRung kAttnRungs[3] = {  // indexed by cc_attn_plan_info.rung
+    {"attn_small", k_attn_small},
+    {"attn_mid", k_attn_mid},
+    {"attn_flash", k_attn_flash}};
+
+// The one launcher: runs what cc::attn_plan says.  `only` >= 0 (the rung
+// entries) additionally requires the plan to land on that rung.
+int attn_launch(int only, const void* qkv, void* out, int64_t n_frames,
+                int seq, int heads, int hidden, float scale,
+                uint64_t stream) {
+  if (!qkv || !out) return cc::set_error(CC_ERR_INVALID, "bad attn args");
+  // 16-byte row loads: rows are 16B multiples at hd == 64, bases must be too
+  if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15))
+    return cc::set_error(CC_ERR_INVALID,
+                         "cc_attn needs 16-byte aligned qkv/out");
+  cc_attn_plan_info plan;
+  if (int rc = cc::attn_plan(n_frames, seq, heads, hidden, &plan)) return rc;
+  const AttnRung& rung = kAttnRungs[plan.rung];
+  if (only >= 0 && only != plan.rung)
+    return cc::set_error(CC_ERR_UNSUPPORTED,
+                         "cc_%s does not cover seq %d, which runs %s (cc_attn "
+                         "picks the rung)",
+                         kAttnRungs[only].label, seq, rung.label);
+  return cc::timed_launch(rung.label, stream, [&] {
+    hipLaunchKernelGGL(rung.kernel, dim3(plan.grid), dim3(plan.block), 0,
+                       (hipStream_t)stream, (const __bf16*)qkv, (__bf16*)out,
+                       (long)n_frames, seq, heads, hidden, scale);
+  });
+}
+
+}  // namespace
+
+extern "C" int cc_attn_plan(int64_t n_frames, int seq, int heads, int hidden,
+                            cc_attn_plan_info* out) {
+  if (!out) return cc::set_error(CC_ERR_INVALID, "cc_attn_plan: null out");
+  return cc::attn_plan(n_frames, seq, heads, hidden, out);
+}
+
+extern "C" int cc_attn(const void* qkv, void* out, int64_t n_frames, int seq,
+                       int heads, int hidden, float scale, uint64_t stream) {
+  return attn_launch(-1, qkv, out, n_frames, seq, heads, hidden, scale,
+                     stream);
+}
+
 extern "C" int cc_attn_small(const void* qkv, void* out, int64_t n_frames,
                              int seq, int heads, int hidden, float scale,
                              uint64_t stream) {
-  if (!qkv || !out || n_frames <= 0 || seq <= 0)
-    return cc::set_error(CC_ERR_INVALID, "bad attn args");
-  if (seq > SMAX || hidden != heads * HD)
-    return cc::set_error(CC_ERR_UNSUPPORTED,
-                         "cc_attn_small needs seq <= 64 and hd == 64");
-  dim3 block(256), grid((unsigned)(n_frames * heads));
-  return cc::timed_launch("attn_small", stream, [&] {
-    hipLaunchKernelGGL(k_attn_small, grid, block, 0, (hipStream_t)stream,
-                       (const __bf16*)qkv, (__bf16*)out, (long)n_frames, seq,
-                       heads, hidden, scale);
-  });
+  return attn_launch(CC_ATTN_SMALL, qkv, out, n_frames, seq, heads, hidden,
+                     scale, stream);
 }
 
 extern "C" int cc_attn_mid(const void* qkv, void* out, int64_t n_frames,
                            int seq, int heads, int hidden, float scale,
                            uint64_t stream) {
-  if (!qkv || !out || n_frames <= 0 || seq <= 0)
-    return cc::set_error(CC_ERR_INVALID, "bad attn args");
-  if (seq <= SMAX || seq > SMID || hidden != heads * HD)
-    return cc::set_error(CC_ERR_UNSUPPORTED,
-                         "cc_attn_mid needs 64 < seq <= 288 and hd == 64");
-  dim3 block(256), grid((unsigned)(n_frames * heads));
-  return cc::timed_launch("attn_mid", stream, [&] {
-    hipLaunchKernelGGL(k_attn_mid, grid, block, 0, (hipStream_t)stream,
-                       (const __bf16*)qkv, (__bf16*)out, (long)n_frames, seq,
-                       heads, hidden, scale);
-  });
+  return attn_launch(CC_ATTN_MID, qkv, out, n_frames, seq, heads, hidden,
+                     scale, stream);
 }
 
 extern "C" int cc_attn_flash(const void* qkv, void* out, int64_t n_frames,
                              int seq, int heads, int hidden, float scale,
                              uint64_t stream) {
-  if (!qkv || !out || n_frames <= 0 || seq <= 0)
-    return cc::set_error(CC_ERR_INVALID, "bad attn args");
-  if (seq <= SMID || hidden != heads * HD)
-    return cc::set_error(CC_ERR_UNSUPPORTED,
-                         "cc_attn_flash is for seq > 288 with hd == 64 "
-                         "(use attn_small/attn_mid below that)");
-  const int n_qtiles = (seq + 63) / 64;
-  dim3 block(256), grid((unsigned)(n_frames * heads * (long)n_qtiles));
-  return cc::timed_launch("attn_flash", stream, [&] {
-    hipLaunchKernelGGL(k_attn_flash, grid, block, 0, (hipStream_t)stream,
-                       (const __bf16*)qkv, (__bf16*)out, (long)n_frames, seq,
-                       heads, hidden, scale);
-  });
+  return attn_launch(CC_ATTN_FLASH, qkv, out, n_frames, seq, heads, hidden,
+                     scale, stream);
 }
+

@@ -37,6 +37,19 @@ class GemmPlan(ctypes.Structure):
     ]
 
 
+class AttnPlan(ctypes.Structure):
+    """cc_attn_plan_info: how a cc_attn call would be launched."""
+
+    _fields_ = [
+        ("rung", ctypes.c_int32),
+        ("grid", ctypes.c_int32),
+        ("block", ctypes.c_int32),
+    ]
+
+
+ATTN_RUNGS = ("small", "mid", "flash")  # cc_attn_plan_info.rung values
+
+
 def _declare(lib: ctypes.CDLL) -> None:
     c = ctypes
     lib.cc_last_error.restype = c.c_char_p
@@ -118,11 +131,14 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.cc_attn_cls.argtypes = [
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64,
         c.c_int, c.c_int, c.c_int, c.c_float, c.c_uint64]
-    lib.cc_attn_small.argtypes = [
+    lib.cc_attn.argtypes = [
         c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int, c.c_int,
         c.c_float, c.c_uint64]
-    lib.cc_attn_mid.argtypes = lib.cc_attn_small.argtypes
-    lib.cc_attn_flash.argtypes = lib.cc_attn_small.argtypes
+    lib.cc_attn_plan.argtypes = [
+        c.c_int64, c.c_int, c.c_int, c.c_int, c.POINTER(AttnPlan)]
+    lib.cc_attn_small.argtypes = lib.cc_attn.argtypes
+    lib.cc_attn_mid.argtypes = lib.cc_attn.argtypes
+    lib.cc_attn_flash.argtypes = lib.cc_attn.argtypes
     lib.cc_layernorm_bf16.argtypes = [
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
         c.c_float, c.c_uint64]
@@ -227,6 +243,15 @@ def gemm_plan(
     check(load().cc_gemm_plan(
         M, N, K, K if lda is None else lda, N if ldr is None else ldr,
         int(has_bias), act, int(has_residual), ctypes.byref(plan)))
+    return plan
+
+
+def attn_plan(n_frames: int, seq: int, heads: int, hidden: int) -> AttnPlan:
+    """The launch plan of a cc_attn call with these arguments (cc_attn_plan;
+    host-only): ``ATTN_RUNGS[plan.rung]`` names the kernel.  Raises on
+    arguments cc_attn itself would reject."""
+    plan = AttnPlan()
+    check(load().cc_attn_plan(n_frames, seq, heads, hidden, ctypes.byref(plan)))
     return plan
 
 

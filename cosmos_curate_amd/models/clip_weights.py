@@ -36,6 +36,7 @@ class VitConfig:
     image: int = 224
     has_cls: bool = True       # SigLIP towers have no class token
     act: str = "quick_gelu"    # "quick_gelu" (CLIP) | "gelu_tanh" (SigLIP)
+    ln_eps: float = 1e-5       # layer_norm_eps: CLIP 1e-5, SigLIP 1e-6
 
     @property
     def num_pos(self) -> int:
@@ -57,7 +58,7 @@ VIT_L14 = VitConfig("vit_l14", hidden=1024, layers=24, heads=16,
 # pooled vector is the embedding; no visual_projection).
 SIGLIP_L16_256 = VitConfig("siglip_l16_256", hidden=1024, layers=24, heads=16,
                            intermediate=4096, patch=16, proj=1024, image=256,
-                           has_cls=False, act="gelu_tanh")
+                           has_cls=False, act="gelu_tanh", ln_eps=1e-6)
 
 CONFIGS = {"vit_b32": VIT_B32, "vit_l14": VIT_L14,
            "siglip_l16_256": SIGLIP_L16_256}

@@ -287,21 +287,43 @@ int cc_gemm_plan(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldr,
                  int has_bias, int act, int has_residual,
                  cc_gemm_plan_info* out);
 
-/* ---- fused short-sequence attention (ViT encoder; replaces torch sdpa
- * + the qkv permute copies).  qkv = the fused-QKV GEMM output
- * [n*seq, 3*hidden] bf16; out [n*seq, hidden] bf16; seq <= 64, head dim
- * 64. */
+/* ---- fused attention (ViT encoder; replaces torch sdpa + the qkv
+ * permute copies).  qkv = the fused-QKV GEMM output [n*seq, 3*hidden]
+ * bf16; out [n*seq, hidden] bf16; head dim 64; qkv and out 16-byte
+ * aligned.  cc_attn runs the rung of the ladder that cc::attn_plan
+ * (csrc/cc_attn_plan.hpp) picks for seq — callers need not know the
+ * thresholds:
+ *   small  everything LDS-resident, one workgroup per (frame, head)
+ *          (ViT-B/32's seq 50)
+ *   mid    Q/K fragments straight from global, V^T + P in LDS, Q in 64-row
+ *          tiles (ViT-L/14's 257, SigLIP-L16-256's 256)
+ *   flash  K/V streamed in 64-row tiles with online softmax, one workgroup
+ *          per (frame, head, q-tile) (SigLIP-384/so400m-class towers)
+ * CC_ERR_INVALID on null or misaligned pointers, non-positive
+ * n_frames/seq/heads or a grid past 2^31-1 workgroups; CC_ERR_UNSUPPORTED
+ * when hidden != heads*64 — all before any launch. */
+int cc_attn(const void* qkv, void* out, int64_t n_frames, int seq, int heads,
+            int hidden, float scale, uint64_t stream);
+
+/* How a cc_attn call with these arguments would be launched.  Host-only,
+ * touches no device.  Validates like cc_attn (same codes and cc_last_error
+ * text), pointers aside. */
+enum { CC_ATTN_SMALL = 0, CC_ATTN_MID = 1, CC_ATTN_FLASH = 2 };
+typedef struct cc_attn_plan_info {
+  int32_t rung;   /* CC_ATTN_SMALL | CC_ATTN_MID | CC_ATTN_FLASH */
+  int32_t grid;   /* workgroups launched */
+  int32_t block;  /* threads per workgroup */
+} cc_attn_plan_info;
+int cc_attn_plan(int64_t n_frames, int seq, int heads, int hidden,
+                 cc_attn_plan_info* out);
+
+/* One rung by name (kernel benches and the per-rung parity tests): cc_attn
+ * restricted to that rung.  A seq the plan gives to another rung returns
+ * CC_ERR_UNSUPPORTED. */
 int cc_attn_small(const void* qkv, void* out, int64_t n_frames, int seq,
                   int heads, int hidden, float scale, uint64_t stream);
-
-/* mid-sequence variant (64 < seq <= 288, head dim 64): ViT-L/14's
- * seq=257.  K/V^T LDS-resident per (frame, head) workgroup, Q in 64-row
- * tiles (replaces torch sdpa on that path). */
 int cc_attn_mid(const void* qkv, void* out, int64_t n_frames, int seq,
                 int heads, int hidden, float scale, uint64_t stream);
-
-/* flash variant (seq > 288, head dim 64): K/V streamed in 64-row tiles
- * with online softmax — covers SigLIP-384/so400m-class towers. */
 int cc_attn_flash(const void* qkv, void* out, int64_t n_frames, int seq,
                   int heads, int hidden, float scale, uint64_t stream);
 

@@ -655,3 +655,92 @@ def test_gemm_plan_matches_execution(lib, M, N, K, act, res, body):
         torch.testing.assert_close(out.float().cpu(), y, rtol=2e-2, atol=8e-2)
     else:
         torch.testing.assert_close(out.cpu(), y, rtol=5e-3, atol=5e-2)
+
+
+def _sdpa_on_fused_qkv(qkv, n, seq, heads, hd, scale):
+    q, k, v = (
+        qkv.reshape(n, seq, 3, heads, hd)[:, :, i].permute(0, 2, 1, 3).float()
+        for i in range(3)
+    )
+    want = torch.nn.functional.scaled_dot_product_attention(q, k, v, scale=scale)
+    return want.permute(0, 2, 1, 3).reshape(n * seq, heads * hd)
+
+
+@pytest.mark.parametrize(
+    ("seq", "rung"),
+    [(1, "small"), (64, "small"), (65, "mid"), (288, "mid"), (289, "flash")],
+)
+def test_attn_picks_the_rung_entry(lib, seq, rung):
+    """cc_attn on both sides of each threshold: the bits of the rung entry
+    the plan names, and sdpa within the rung tests' tolerance."""
+    import ctypes
+
+    n, heads, hd = 2, 2, 64
+    hidden = heads * hd
+    assert hotpath.ATTN_RUNGS[hotpath.attn_plan(n, seq, heads, hidden).rung] == rung
+    torch.manual_seed(seq)
+    qkv = (torch.randn(n * seq, 3 * hidden) * 0.5).to(torch.bfloat16).cuda()
+    scale = ctypes.c_float(hd ** -0.5)
+    stream = torch.cuda.current_stream().cuda_stream
+    outs = []
+    for fn in (lib.cc_attn, getattr(lib, f"cc_attn_{rung}")):
+        out = torch.zeros(n * seq, hidden, dtype=torch.bfloat16, device="cuda")
+        hotpath.check(fn(qkv.data_ptr(), out.data_ptr(), n, seq, heads, hidden,
+                         scale, stream))
+        outs.append(out)
+    torch.cuda.synchronize()
+    assert torch.equal(outs[0], outs[1])
+    want = _sdpa_on_fused_qkv(qkv, n, seq, heads, hd, hd ** -0.5)
+    torch.testing.assert_close(outs[0].float(), want, rtol=2e-2, atol=2e-2)
+
+
+def test_attn_rejects_before_launch(lib):
+    """Misaligned pointers and heads == 0 (where hidden == heads*64 holds
+    trivially) are refused, and nothing is launched: out stays untouched
+    and no launch is counted."""
+    import ctypes
+
+    n, seq, heads, hidden = 2, 8, 2, 128
+    qkv = torch.zeros(n * seq + 1, 3 * hidden, dtype=torch.bfloat16, device="cuda")
+    out = torch.full((n * seq + 1, hidden), 7.0, dtype=torch.bfloat16, device="cuda")
+    scale = ctypes.c_float(0.125)
+    hotpath.timing_enable(True)
+    try:
+        for fn in (lib.cc_attn, lib.cc_attn_small):
+            for args in (
+                (qkv.data_ptr() + 2, out.data_ptr(), n, seq, heads, hidden),
+                (qkv.data_ptr(), out.data_ptr() + 2, n, seq, heads, hidden),
+                (qkv.data_ptr(), out.data_ptr(), n, seq, 0, 0),
+            ):
+                assert fn(*args, scale, 0) < 0
+                assert lib.cc_last_error()
+        torch.cuda.synchronize()
+        assert hotpath.timing_report("attn_small")[1] == 0
+    finally:
+        hotpath.timing_enable(False)
+    assert torch.all(out == 7.0)
+
+
+@pytest.mark.parametrize("image", [32, 144, 288])  # seq 4 / 81 / 324
+def test_siglip_tiny_gpu_vs_oracle_cosine(lib, image):
+    """A 2-layer SigLIP tower through the shared encoder on the GPU, one
+    sequence length per attention rung, vs transformers fp32."""
+    from cosmos_curate_amd.models import clip_weights as cw
+    from cosmos_curate_amd.models.siglip_vit import SiglipVisionTowerAMD
+    from oracle.vit import build_reference_siglip_vision, siglip_embed_frames_fp32
+
+    cfg = cw.VitConfig("siglip_tiny", hidden=128, layers=2, heads=2,
+                       intermediate=256, patch=16, proj=128, image=image,
+                       has_cls=False, act="gelu_tanh", ln_eps=1e-6)
+    sd = cw.make_siglip_weights(cfg)
+    ref = build_reference_siglip_vision(
+        sd, dict(hidden_size=128, intermediate_size=256, num_hidden_layers=2,
+                 num_attention_heads=2, image_size=image, patch_size=16))
+    torch.manual_seed(image)
+    pix = torch.rand(2, 3, image, image) * 2 - 1  # SigLIP-normalized range
+    want = siglip_embed_frames_fp32(ref, pix)
+    tower = SiglipVisionTowerAMD(sd, cfg).cuda()
+    got = tower(pix.cuda().to(torch.bfloat16)).cpu().numpy()
+    cos = (got * want).sum(axis=1)
+    print("per-frame cosine vs fp32 oracle:", cos.tolist())
+    assert np.all(cos >= 0.999), cos

@@ -28,6 +28,8 @@ def _torch_linear(self, x, w, b, act=0, residual=None):
     y = torch.nn.functional.linear(x.float(), w.float(), b.float() if b is not None else None)
     if act == 1:
         y = y * torch.sigmoid(1.702 * y)
+    if act == 2:
+        y = torch.nn.functional.gelu(y, approximate="tanh")
     if residual is not None:
         y = y + residual.float()
     return y.to(torch.bfloat16)
@@ -114,6 +116,62 @@ def test_siglip_weights_load_into_transformers():
     import numpy as np
 
     np.testing.assert_allclose((e ** 2).sum(axis=1), 1.0, rtol=1e-5)
+
+
+def _tiny_siglip(image):
+    """(cfg, weights) of a 2-layer, 2-head (hd 64) SigLIP tower."""
+    from cosmos_curate_amd.models.clip_weights import VitConfig, make_siglip_weights
+
+    cfg = VitConfig("siglip_tiny", hidden=128, layers=2, heads=2,
+                    intermediate=256, patch=16, proj=128, image=image,
+                    has_cls=False, act="gelu_tanh", ln_eps=1e-6)
+    return cfg, make_siglip_weights(cfg)
+
+
+@pytest.mark.parametrize("image", [32, 144])  # seq 4 and 81
+def test_siglip_tower_matches_transformers_fp32(monkeypatch, image):
+    """SiglipVisionTowerAMD's own arithmetic (patch bias, position add, the
+    shared encoder at act 2 / eps 1e-6, post-LN, MAP head) vs transformers
+    SiglipVisionModel fp32, _linear patched to torch."""
+    from cosmos_curate_amd.models.siglip_vit import SiglipVisionTowerAMD
+
+    cfg, sd = _tiny_siglip(image)
+    ref = oracle_vit.build_reference_siglip_vision(
+        sd, dict(hidden_size=128, intermediate_size=256, num_hidden_layers=2,
+                 num_attention_heads=2, image_size=image, patch_size=16))
+    torch.manual_seed(image)
+    pixels = torch.rand(2, 3, image, image) * 2 - 1  # SigLIP-normalized range
+    want = oracle_vit.siglip_embed_frames_fp32(ref, pixels)
+
+    monkeypatch.setattr(SiglipVisionTowerAMD, "_linear", _torch_linear)
+    got = SiglipVisionTowerAMD(sd, cfg)(pixels).numpy()
+    assert want.shape == got.shape == (2, 128)
+    cos = np.sum(want * got, axis=1)  # both unit-norm
+    print("per-frame cosine vs fp32 oracle:", cos.tolist())
+    assert np.all(cos >= 0.999), cos
+
+
+def test_siglip_tower_linear_calls(monkeypatch):
+    """The shared layer loop as SigLIP drives it: the patch GEMM (with its
+    bias) and 4 GEMMs per layer, every one on all n*seq rows; the fc1
+    epilogue carries the tanh-gelu code and nothing else an activation."""
+    from cosmos_curate_amd.models.siglip_vit import SiglipVisionTowerAMD
+
+    cfg, sd = _tiny_siglip(32)
+    calls = []
+
+    def counting(self, x, w, b, act=0, residual=None):
+        calls.append((x.shape[0], b is not None, act, residual is not None))
+        return _torch_linear(self, x, w, b, act, residual)
+
+    monkeypatch.setattr(SiglipVisionTowerAMD, "_linear", counting)
+    n, seq = 3, 4
+    SiglipVisionTowerAMD(sd, cfg)(torch.randn(n, 3, 32, 32))
+    rows = n * seq
+    layer = [(rows, True, 0, False), (rows, True, 0, True),   # qkv, out+res
+             (rows, True, 2, False), (rows, True, 0, True)]   # fc1, fc2+res
+    assert calls == [(rows, True, 0, False)] + layer * cfg.layers
+    assert len(calls) == 1 + 4 * cfg.layers
 
 
 def test_siglip_config_geometry():
