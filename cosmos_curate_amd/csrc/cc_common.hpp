@@ -26,6 +26,9 @@ inline int set_error(int code, const char* fmt, ...) {
   return code;
 }
 
+// the row widths the LayerNorm kernels are instantiated for (cc_ln.hip)
+bool ln_h_supported(int64_t H);
+
 // ---- kernel timing registry (hipEvent based, see cc_timing_* ABI) ----
 // Launches are bracketed with event pairs on their stream but NOT
 // synchronized at launch time (that would serialize the pipeline and

@@ -127,12 +127,19 @@ __device__ __forceinline__ bf16x8 frag_read(const __bf16* tile, int row,
 // for dense operands; larger when the rows are a strided subset of a
 // bigger tensor (the CLS rows of [frames*seq, hidden]).  B and C are
 // always dense.
-template <int ACT, bool HAS_BIAS, bool HAS_RES>  // ACT 1 = quick-gelu
+//
+// LN_IN (both bodies): A is the raw input of a LayerNorm
+// whose affine part is folded into B, and the epilogue finishes the
+// normalisation per row before the activation:
+//   act(rstd_m * (acc - mean_m * colsum[n]) + bias[n])
+// with murstd[m] = (mean, rstd) of A's row m and bias = W beta + b.
+template <int ACT, bool HAS_BIAS, bool HAS_RES, bool LN_IN>  // ACT 1 = quick-gelu
 __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
     const __bf16* __restrict__ A, const __bf16* __restrict__ B,
     void* __restrict__ C, const float* __restrict__ bias,
     const __bf16* __restrict__ residual, long M, long N, long K, long lda,
-    long ldr, int c_is_bf16, int nbx, int nwg, int do_remap) {
+    long ldr, int c_is_bf16, int nbx, int nwg, int do_remap,
+    const float* __restrict__ colsum, const float2* __restrict__ murstd) {
   __shared__ __bf16 lds[2 * (BM + BN) * BK];  // one __shared__ object (G16 4a)
 #define AS(b) (lds + (b) * (BM * BK))
 #define BS(b) (lds + 2 * (BM * BK) + (b) * (BN * BK))
@@ -207,11 +214,22 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
   if (interior) {
 #pragma unroll
     for (int m = 0; m < MFR; m++) {
+      float2 mr[4] = {};  // LN_IN: (mean, rstd) of this fragment's 4 rows
+      if constexpr (LN_IN) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) mr[r] = murstd[crow_base + m * FRAG + r];
+      }
 #pragma unroll
       for (int n = 0; n < NFR; n++) {
         const long col = ccol_base + n * FRAG;
         float bval = 0.0f;
         if constexpr (HAS_BIAS) bval = bias[col];
+        if constexpr (LN_IN) {
+          const float sval = colsum[col];
+#pragma unroll
+          for (int r = 0; r < 4; r++)
+            acc[m][n][r] = mr[r].y * (acc[m][n][r] - mr[r].x * sval);
+        }
         // batch the residual loads (independent, one wait) before the
         // store sequence — an interleaved load/store chain serializes
         float rv[4];
@@ -246,6 +264,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
       for (int r = 0; r < 4; r++) {
         const long row = crow_base + m * FRAG + r;
         if (row >= M) continue;
+        if constexpr (LN_IN) {
+          const float2 mr = murstd[row];
+          acc[m][n][r] = mr.y * (acc[m][n][r] - mr.x * colsum[col]);
+        }
         float v = cc_act<ACT>(acc[m][n][r] + bval);
         if constexpr (HAS_RES) v += (float)residual[row * ldr + col];
         if (c_is_bf16)
@@ -264,8 +286,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
 // ... v22; round-2 ladder in DESIGN.md §9a) ----
 // 512 threads = 8 waves (2M x 4N), per-wave 128x64 = 8x4 frags; LDS
 // 128 KiB; PERSISTENT fleet (grid = min(nwg, 256)); raw s_barrier
-// phases; COUNTED vmcnt(4) publishes at tile tops (B(t+2) spans each
-// boundary in flight); T19 scheduler weave of next-phase ds_reads into
+// phases; COUNTED vmcnt(4) publish before the last barrier of each K-tile
+// (B(t+2) spans each boundary in flight); T19 scheduler weave of next-phase ds_reads into
 // the MFMA clusters; template-selected epilogue (LDS-staged coalesced
 // for fused bias/act/residual, scalar otherwise; EPI_STAGED is always
 // ACT != 0 || HAS_BIAS || HAS_RES).  Which shapes it serves is
@@ -277,12 +299,50 @@ constexpr int WM2 = 128, WN2 = 64;
 constexpr int MFR2 = WM2 / FRAG;  // 8
 constexpr int NFR2 = WN2 / FRAG;  // 4
 
-template <int ACT, bool HAS_BIAS, bool HAS_RES, bool EPI_STAGED>
+//
+// LN_IN: the folded-LayerNorm epilogue (see k_gemm_bf16).  The tile's 256
+// (mean, rstd) pairs are a 2 KB LDS table behind the 128 KiB of operand
+// buffers, staged like the operands: one 4-byte-wide glds per wave (its
+// 32 rows), issued with the tile's prologue, landed by the rep-top
+// vmcnt(0) and published by the rep-top barrier; the epilogue reads it.
+// No VGPR carries it (a register-held pair was spilled around the
+// epilogue and its vmcnt(0) exposed one load latency per tile).  TWO
+// tables, alternating per tile: tile r+1's glds is issued before tile r's
+// epilogue reads table r.  Table (r+1)&1 was last read in epilogue r-1,
+// which every wave left before any wave passed rep-top barrier r, and the
+// glds is issued after that.
+//
+// STATS: the epilogue also writes the LayerNorm statistics of the C rows
+// it stores, stats[row][col/64] = (sum, sum of squares) over the wave's
+// 64 columns of that row, taken in f32 from the rounded bf16 values.  In
+// the staged read-back 8 adjacent lanes hold one row's 64 columns, so it
+// is 3 DPP adds per value, no LDS, no barrier.  Needs N % 64 == 0.
+// LN_IN and STATS launches are bf16-out and always staged.
+constexpr int LN_TAB = BM2 * 4;  // one table: 256 float2 = 2 KB, in bf16 elements
+
+// v + (the same value in the lane DPP control CTRL names)
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+  const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v),
+                                            CTRL, 0xf, 0xf, false);
+  return v + __builtin_bit_cast(float, o);
+}
+// sum over each aligned group of 8 lanes (every lane gets the total):
+// quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror
+__device__ __forceinline__ float sum8(float v) {
+  return dpp_add<0x141>(dpp_add<0x4e>(dpp_add<0xb1>(v)));
+}
+
+template <int ACT, bool HAS_BIAS, bool HAS_RES, bool EPI_STAGED, bool LN_IN,
+          bool STATS>
 __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
     const __bf16* __restrict__ A, const __bf16* __restrict__ B,
     void* __restrict__ C, const float* __restrict__ bias,
     const __bf16* __restrict__ residual, long M, long N, long K,
-    int c_is_bf16, int nbx, int nwg, int order_mode) {
+    int c_is_bf16, int nbx, int nwg, int order_mode,
+    const float* __restrict__ colsum, const float2* __restrict__ murstd,
+    float2* __restrict__ stats) {
+  static_assert(!STATS || HAS_RES, "the stats epilogue is the residual one");
   // Round-2 structure: PERSISTENT multi-tile (grid = min(nwg, 256), one
   // WG per CU) around the round-1 8-phase glds schedule.  Each WG walks
   // tiles bid, bid+grid, ... and issues the NEXT tile's 12-glds
@@ -294,7 +354,24 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
   // stride; 1 = stride + bijective XCD remap (skinny-N grids, L2 row
   // sharing).  Sync structure per K-tile is UNCHANGED from the
   // race-screened v11 (vmcnt(0) publish at ph3, leading barriers).
-  __shared__ __bf16 lds[2 * (BM2 + BN2) * BK];  // 128 KiB
+  // 128 KiB (+ the two 2 KB (mean, rstd) tables under LN_IN)
+  __shared__ __bf16 lds[2 * (BM2 + BN2) * BK + (LN_IN ? 2 * LN_TAB : 0)];
+// table b; this wave stages dwords [64 wid, 64 wid + 64) of it: dword d is
+// component d & 1 of tile row d >> 1, the row clamped like the A rows
+#define LNTAB(b) ((float*)(lds + 2 * (BM2 + BN2) * BK + (b) * LN_TAB))
+#define STAGE_LN2(b)                                                        \
+  do {                                                                      \
+    if constexpr (LN_IN) {                                                  \
+      const long r = bm + (tid >> 1);                                       \
+      const float* g = (const float*)(murstd + (r < M ? r : M - 1)) +       \
+                       (tid & 1);                                           \
+      __builtin_amdgcn_global_load_lds(                                     \
+          (const __attribute__((address_space(1))) unsigned int*)g,         \
+          (__attribute__((address_space(3))) unsigned int*)(LNTAB(b) +      \
+                                                            wid * 64),      \
+          4, 0, 0);                                                         \
+    }                                                                       \
+  } while (0)
 #define A2T(b) (lds + (b) * (BM2 * BK))
 #define B2T(b) (lds + 2 * (BM2 * BK) + (b) * (BN2 * BK))
   const int tid = threadIdx.x;
@@ -326,6 +403,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
   }
   // first prologue: A(0) h0,h1, B(0) h0,h1, B(1) h0,h1 (12 glds); later
   // tiles' prologues issue under the previous epilogue.
+  STAGE_LN2(0);
   STAGE_A2(0, 0);
   STAGE_A2(0, 1);
   STAGE_B2(0, 0);
@@ -397,12 +475,9 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
   do {                                                                      \
     const __bf16* At = A2T((t) & 1);                                        \
     const __bf16* Bt = B2T((t) & 1);                                        \
-    /* counted publish for THIS tile's operands, placed as late as      */ \
-    /* possible (after the previous tile's MFMA(3) instead of before    */ \
-    /* it): newest-first per-wave queue here is [B(t+1):4, A(t):4, ...] */ \
-    /* so vmcnt(4) retires A(t)/B(t) and keeps B(t+1) in flight.  At    */ \
-    /* tile 0 of a rep the queue is already drained (rep-top vmcnt(0))  */ \
-    /* and this is a no-op.                                             */ \
+    /* no-op since the publish below moved back before the barrier (the */ \
+    /* queue holds only B(t+1):4 here, or nothing at tile 0 of a rep);  */ \
+    /* kept as the compiler fence the measured schedule was built with  */ \
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                        \
     READ_B2(Bt);                                                            \
     READ_A2(At, 0);                                                         \
@@ -432,8 +507,16 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
     if ((t) + 2 < KT) {                                                     \
       STAGE_B2((t) + 2, 0);                                                 \
       STAGE_B2((t) + 2, 1);                                                 \
-      /* publish moved to the NEXT tile's top (one more MFMA cluster of  */ \
-      /* latency cover at the same count)                                */ \
+      /* The wait sits HERE, before the barrier.  For a while it sat at  */ \
+      /* the next tile's top (one more MFMA cluster of latency cover):   */ \
+      /* that retires only the waiting wave's own loads, and the reads   */ \
+      /* right after it take rows other waves staged, with no barrier    */ \
+      /* after THEIR wait - a late load was read stale.  Dormant until   */ \
+      /* the folded-LN route changed the memory traffic around the GEMMs */ \
+      /* (1-7 of 224 bench rows off by ~1e-4 in 6 of 6 runs; 0 of 6 with */ \
+      /* the wait here, profiles/r04_lnfold_det.txt).  Rule: counted     */ \
+      /* wait, then a barrier, then the first read*/ \
+      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                      \
     } else {                                                                \
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* tail drain */     \
     }                                                                       \
@@ -460,6 +543,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
       if (order_mode == 1) orig = xcd_remap(orig, nwg);
       bm = (long)(orig / nbx) * BM2;
       bn = (long)(orig % nbx) * BN2;
+      STAGE_LN2((rep + 1) & 1);
       STAGE_A2(0, 0);
       STAGE_A2(0, 1);
       STAGE_B2(0, 0);
@@ -485,7 +569,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
     // the scalar path, inside the embedding-cosine contract.
     const long crow_base = ebm + waveM * WM2 + 4 * (lane >> 4);
     const long ccol_base = ebn + waveN * WN2 + (lane & 15);
-    if (c_is_bf16 && EPI_STAGED) {
+    if ((c_is_bf16 && EPI_STAGED) || LN_IN || STATS) {
       __bf16* slice = A2T(1) + wid * 2048;  // 4 KB per wave
       const long wrow0 = ebm + waveM * WM2;
       const long wcol0 = ebn + waveN * WN2;
@@ -499,11 +583,26 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
           bhoist[n] = (col < N) ? bias[col] : 0.0f;
         }
       }
+      float shoist[NFR2] = {};  // LN_IN: column sums of the folded weight
+      if constexpr (LN_IN) {
+#pragma unroll
+        for (int n = 0; n < NFR2; n++) {
+          const long col = ccol_base + n * FRAG;
+          shoist[n] = (col < N) ? colsum[col] : 0.0f;
+        }
+      }
 #pragma unroll
       for (int p = 0; p < 4; p++) {
 #pragma unroll
         for (int mm = 0; mm < 2; mm++) {
           const int m = 2 * p + mm;
+          float2 mr[4] = {};  // LN_IN: (mean, rstd) of this lane's 4 rows
+          if constexpr (LN_IN) {
+            const float2* t = (const float2*)LNTAB(rep & 1) + waveM * WM2 +
+                              m * FRAG + 4 * (lane >> 4);
+#pragma unroll
+            for (int r = 0; r < 4; r++) mr[r] = t[r];
+          }
 #pragma unroll
           for (int n = 0; n < NFR2; n++) {
             const float bval = bhoist[n];
@@ -511,6 +610,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
             const int lcol = n * FRAG + (lane & 15);
 #pragma unroll
             for (int r = 0; r < 4; r++) {
+              if constexpr (LN_IN)
+                acc[m][n][r] = mr[r].y * (acc[m][n][r] - mr[r].x * shoist[n]);
               float v = cc_act<ACT>(acc[m][n][r] + bval);
               *(unsigned short*)(slice + (lrow_b + r) * 64 + lcol) =
                   f32_to_bf16_rne(v);
@@ -525,6 +626,30 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
           const int lcol8 = elem & 63;         // 8-elem aligned
           const long grow = wrow0 + p * 32 + lrow;
           const long gcol = wcol0 + lcol8;
+          if constexpr (STATS) {
+            // the 8 lanes of a row share grow and (N % 64 == 0) the side
+            // of the N edge, so `ok` is uniform over each sum8 group; the
+            // adds run on every lane, outside the branch
+            const bool ok = grow < M && gcol < N;
+            float s = 0.0f, ss = 0.0f;
+            if (ok) {
+              bf16x8 v8 = *(const bf16x8*)(slice + elem);
+              const bf16x8 r8 = *(const bf16x8*)(residual + grow * N + gcol);
+#pragma unroll
+              for (int e = 0; e < 8; e++) {
+                v8[e] = (__bf16)((float)v8[e] + (float)r8[e]);
+                const float f = (float)v8[e];
+                s += f;
+                ss += f * f;
+              }
+              *(bf16x8*)((__bf16*)C + grow * N + gcol) = v8;
+            }
+            s = sum8(s);
+            ss = sum8(ss);
+            if (ok && (lane & 7) == 0)
+              stats[grow * (N >> 6) + (gcol >> 6)] = make_float2(s, ss);
+            continue;
+          }
           if (grow >= M || gcol >= N) continue;  // N % 8 == 0 always
           bf16x8 v8 = *(const bf16x8*)(slice + elem);
           if constexpr (HAS_RES) {
@@ -573,6 +698,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
       }
     }
   }
+#undef LNTAB
+#undef STAGE_LN2
 #undef A2T
 #undef B2T
 #undef STAGE_A2
@@ -591,26 +718,33 @@ struct GemmArgs {
   long M, N, K, lda, ldr;
   int c_is_bf16;
   hipStream_t stream;
+  // folded-LayerNorm launches only (LN_IN / STATS)
+  const float* colsum = nullptr;
+  const float2* murstd = nullptr;
+  float2* stats = nullptr;
 };
 
-// One launch per (ACT, HAS_BIAS, HAS_RES); the plan picks the body.  The
-// 256² epilogue is a TEMPLATE parameter fixed by the same three, not a
-// runtime branch: carrying both epilogues in one instantiation spilled
-// VGPRs in the rep loop and cost ~10% bare (profiles/r02_t19_sweep.log,
-// prod column vs the single-epilogue tool kernels).
-template <int ACT, bool HB, bool HR>
+// One launch per (ACT, HAS_BIAS, HAS_RES, LN_IN, STATS); the plan picks
+// the body.  The 256² epilogue is a TEMPLATE parameter fixed by the same
+// five, not a runtime branch: carrying both epilogues in one instantiation
+// spilled VGPRs in the rep loop and cost ~10% bare
+// (profiles/r02_t19_sweep.log, prod column vs the single-epilogue tool
+// kernels).  The 128² body has no STATS form: cc_gemm_bf16_res_stats
+// follows it with the stand-alone stats kernel.
+template <int ACT, bool HB, bool HR, bool LN = false, bool ST = false>
 void gemm_run(const cc_gemm_plan_info& p, const GemmArgs& g) {
   const int nwg = p.tiles_x * p.tiles_y;
   if (p.body == cc::GEMM_T256)
     hipLaunchKernelGGL(
-        (k_gemm_bf16_t256<ACT, HB, HR, ACT != 0 || HB || HR>), dim3(p.grid),
-        dim3(p.block), 0, g.stream, g.A, g.B, g.C, g.bias, g.residual, g.M,
-        g.N, g.K, g.c_is_bf16, p.tiles_x, nwg, p.xcd_remap);
+        (k_gemm_bf16_t256<ACT, HB, HR, ACT != 0 || HB || HR, LN, ST>),
+        dim3(p.grid), dim3(p.block), 0, g.stream, g.A, g.B, g.C, g.bias,
+        g.residual, g.M, g.N, g.K, g.c_is_bf16, p.tiles_x, nwg, p.xcd_remap,
+        g.colsum, g.murstd, g.stats);
   else
-    hipLaunchKernelGGL((k_gemm_bf16<ACT, HB, HR>), dim3(p.grid),
+    hipLaunchKernelGGL((k_gemm_bf16<ACT, HB, HR, LN>), dim3(p.grid),
                        dim3(p.block), 0, g.stream, g.A, g.B, g.C, g.bias,
                        g.residual, g.M, g.N, g.K, g.lda, g.ldr, g.c_is_bf16,
-                       p.tiles_x, nwg, p.xcd_remap);
+                       p.tiles_x, nwg, p.xcd_remap, g.colsum, g.murstd);
 }
 
 using GemmRunFn = void (*)(const cc_gemm_plan_info&, const GemmArgs&);
@@ -621,6 +755,13 @@ constexpr GemmRunFn kGemmRun[3][2][2] = {  // [act][has_bias][has_residual]
      {gemm_run<1, true, false>, gemm_run<1, true, true>}},
     {{gemm_run<2, false, false>, gemm_run<2, false, true>},
      {gemm_run<2, true, false>, gemm_run<2, true, true>}}};
+// folded-LayerNorm consumers: bias (= W beta + b) always, no residual
+constexpr GemmRunFn kGemmRunLn[3] = {  // [act]
+    gemm_run<0, true, false, true>, gemm_run<1, true, false, true>,
+    gemm_run<2, true, false, true>};
+
+// act: 1 quick-gelu, 2 tanh-gelu (SigLIP), anything else none
+int act_index(int act) { return act == 1 ? 1 : act == 2 ? 2 : 0; }
 
 int gemm_launch(const void* A, int64_t lda, const void* B, void* C, int64_t M,
                 int64_t N, int64_t K, const float* bias, int c_dtype, int act,
@@ -634,10 +775,8 @@ int gemm_launch(const void* A, int64_t lda, const void* B, void* C, int64_t M,
                       (const __bf16*)residual, (long)M, (long)N, (long)K,
                       (long)lda, (long)ldr, c_dtype == 1 ? 1 : 0,
                       (hipStream_t)stream};
-  // act: 1 quick-gelu, 2 tanh-gelu (SigLIP), anything else none
   return cc::timed_launch("gemm_bf16", stream, [&] {
-    kGemmRun[act == 1 ? 1 : act == 2 ? 2 : 0][bias != nullptr]
-            [residual != nullptr](plan, args);
+    kGemmRun[act_index(act)][bias != nullptr][residual != nullptr](plan, args);
   });
 }
 }  // namespace
@@ -671,4 +810,63 @@ extern "C" int cc_gemm_bf16(const void* A, const void* B, void* C, int64_t M,
                             int64_t N, int64_t K, const float* bias,
                             int c_dtype, uint64_t stream) {
   return cc_gemm_bf16_ex(A, B, C, M, N, K, bias, c_dtype, 0, nullptr, stream);
+}
+
+extern "C" int cc_gemm_bf16_res_stats(const void* A, const void* B, void* C,
+                                      int64_t M, int64_t N, int64_t K,
+                                      const float* bias, const void* residual,
+                                      void* stats, uint64_t stream) {
+  if (!A || !B || !C || !bias || !residual || !stats)
+    return cc::set_error(CC_ERR_INVALID, "bad gemm_res_stats args");
+  if (!cc::ln_h_supported(N))
+    return cc::set_error(CC_ERR_UNSUPPORTED,
+                         "gemm_res_stats: no LayerNorm statistics at N %lld",
+                         (long long)N);
+  cc_gemm_plan_info plan;
+  if (int rc = cc::gemm_plan(M, N, K, K, N, true, 0, true,
+                             cc::gemm_env_knobs(), &plan))
+    return rc;
+  GemmArgs args{(const __bf16*)A, (const __bf16*)B, C, bias,
+                (const __bf16*)residual, (long)M, (long)N, (long)K, (long)K,
+                (long)N, 1, (hipStream_t)stream};
+  if (plan.body == cc::GEMM_T256 && cc::gemm_env_knobs().fuse_stats) {
+    args.stats = (float2*)stats;
+    return cc::timed_launch("gemm_bf16", stream, [&] {
+      gemm_run<0, true, true, false, true>(plan, args);
+    });
+  }
+  if (int rc = cc::timed_launch("gemm_bf16", stream, [&] {
+        gemm_run<0, true, true>(plan, args);
+      }))
+    return rc;
+  return cc_ln_stats_bf16(C, M, N, stats, stream);
+}
+
+extern "C" int cc_gemm_bf16_ln(const void* A, int64_t row_step,
+                               const void* stats, void* murstd,
+                               const void* Wfold, const float* colsum,
+                               const float* cbias, void* C, int64_t M,
+                               int64_t N, int64_t K, int act, float eps,
+                               uint64_t stream) {
+  if (!A || !stats || !murstd || !Wfold || !colsum || !cbias || !C ||
+      row_step <= 0)
+    return cc::set_error(CC_ERR_INVALID, "bad gemm_ln args");
+  if (!cc::ln_h_supported(K))
+    return cc::set_error(CC_ERR_UNSUPPORTED,
+                         "gemm_ln: no LayerNorm statistics at K %lld",
+                         (long long)K);
+  cc_gemm_plan_info plan;
+  if (int rc = cc::gemm_plan(M, N, K, row_step * K, N, true, act, false,
+                             cc::gemm_env_knobs(), &plan))
+    return rc;
+  if (int rc = cc_ln_finalize(stats, M, K, row_step, eps, murstd, stream))
+    return rc;
+  GemmArgs args{(const __bf16*)A, (const __bf16*)Wfold, C, cbias, nullptr,
+                (long)M, (long)N, (long)K, (long)(row_step * K), (long)N, 1,
+                (hipStream_t)stream};
+  args.colsum = colsum;
+  args.murstd = (const float2*)murstd;
+  return cc::timed_launch("gemm_bf16", stream, [&] {
+    kGemmRunLn[act_index(act)](plan, args);
+  });
 }

@@ -21,6 +21,9 @@ constexpr int GEMM_FLEET = 256; // persistent fleet: one 256² WG per CU
 struct GemmKnobs {
   int tile = -1;    // CC_GEMM_TILE: 0 / 1 force the 128² / 256² body
   int persist = 1;  // CC_GEMM_PERSIST: 0 = one 256² tile per WG
+  // CC_GEMM_FUSE_STATS: 0 = cc_gemm_bf16_res_stats runs the plain residual
+  // GEMM and the stand-alone stats kernel on the 256² body too
+  int fuse_stats = 1;
 };
 
 inline const GemmKnobs& gemm_env_knobs() {
@@ -28,6 +31,7 @@ inline const GemmKnobs& gemm_env_knobs() {
     GemmKnobs v;
     if (const char* e = getenv("CC_GEMM_TILE")) v.tile = atoi(e);
     if (const char* e = getenv("CC_GEMM_PERSIST")) v.persist = atoi(e);
+    if (const char* e = getenv("CC_GEMM_FUSE_STATS")) v.fuse_stats = atoi(e);
     return v;
   }();
   return k;

@@ -1,7 +1,9 @@
 // Fused bf16 LayerNorm — row-wise (x - mean)/sqrt(var + eps) * w + b.
 //
-// Replaces torch-rocm's vectorized_layer_norm in the ViT forward (26
-// calls/step at ~2 TB/s effective, ~10% of the bench step).  Stats in
+// Replaces torch-rocm's vectorized_layer_norm in the ViT forward.  Since
+// LN1/LN2 are folded into the GEMMs that consume them it
+// runs 2 calls/step at the bench shape (LN2 at M = frames and the post-LN
+// on the CLS rows); with the fold off, 25 at ~5.9 TB/s.  Stats in
 // f32 (torch layer_norm opmath semantics), bf16 in/out, f32 affine
 // params.  One wave per row: H/64 elements per lane, two shfl_xor
 // reduction trees (sum, sumsq), bf16x4 (8 B) loads/stores (guide §5
@@ -9,7 +11,15 @@
 // measured 4.7 TB/s at bf16x2).
 // H must be a multiple of 256 (768/1024/3072/4096 all comply).
 //
-// Also here: cc_embed_assemble_ln — the ViT embedding assembly
+// Also here: the row statistics of the folded LayerNorm.
+// cc_ln_stats_bf16 reads x once and writes f32 partial sums (sum, sum of
+// squares) per 64-column block, [M, H/64, 2] — the layout the residual
+// GEMM's epilogue also fills (cc_gemm.hip); cc_ln_finalize adds a row's
+// partials in index order and writes (mean, rstd) [M, 2] for the
+// consuming GEMM's epilogue.  No atomics, fixed order: bit-identical from
+// run to run.
+//
+// And cc_embed_assemble_ln — the ViT embedding assembly
 // ([CLS; patch tokens] + position embedding, then pre-LN) fused into
 // one pass.  Replaces a torch cat + f32 add + bf16 cast + layer_norm
 // chain (4 kernel launches, ~300 us/step at the bench shape) with one
@@ -163,6 +173,82 @@ __global__ void k_layernorm_bf16_h128(const __bf16* __restrict__ x,
   *(bf16x2*)(yr + i0) = o;
 }
 
+// sum over each aligned group of 2^k lanes, every lane gets the total
+template <int GROUP>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int off = GROUP / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// stats[row][blk] = (sum, sum of squares) of x[row][64*blk .. 64*blk+63];
+// one wave per row, read-only on x.  Lane i of step c holds columns
+// c*64 + 4i .. +3, so 16 adjacent lanes hold one 64-column block.
+template <int CHUNK>
+__global__ void k_ln_stats_bf16(const __bf16* __restrict__ x,
+                                float2* __restrict__ stats, long M, int H) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const long row = (long)blockIdx.x * 4 + wave;
+  if (row >= M) return;
+  const __bf16* xr = x + row * H;
+  float2* sr = stats + row * CHUNK;
+#pragma unroll
+  for (int c = 0; c < CHUNK; c += 4) {
+    bf16x4 p = *(const bf16x4*)(xr + c * 64 + 4 * lane);
+    float s = 0.0f, ss = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const float v = (float)p[j];
+      s += v;
+      ss += v * v;
+    }
+    s = group_sum<16>(s);
+    ss = group_sum<16>(ss);
+    if ((lane & 15) == 0) sr[c + (lane >> 4)] = make_float2(s, ss);
+  }
+}
+
+// H = 128: 2 elements per lane, 32 lanes per 64-column block
+__global__ void k_ln_stats_bf16_h128(const __bf16* __restrict__ x,
+                                     float2* __restrict__ stats, long M) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const long row = (long)blockIdx.x * 4 + wave;
+  if (row >= M) return;
+  bf16x2 p = *(const bf16x2*)(x + row * 128 + 2 * lane);
+  const float v0 = (float)p.x, v1 = (float)p.y;
+  const float s = group_sum<32>(v0 + v1);
+  const float ss = group_sum<32>(v0 * v0 + v1 * v1);
+  if ((lane & 31) == 0) stats[row * 2 + (lane >> 5)] = make_float2(s, ss);
+}
+
+// murstd[r] = (mean, rstd) of stats row r * row_step: 8 lanes per row,
+// lane j adds partials j, j+8, ... in that order, then a 3-step tree.
+// Same form as k_layernorm_bf16: var = sumsq/H - mean^2, rsqrtf(var+eps).
+__global__ void k_ln_finalize(const float2* __restrict__ stats,
+                              float2* __restrict__ murstd, long M, int P,
+                              long row_step, float inv_n, float eps) {
+  const long row = ((long)blockIdx.x * 256 + threadIdx.x) >> 3;
+  const int j = threadIdx.x & 7;
+  float s = 0.0f, ss = 0.0f;
+  if (row < M) {
+    const float2* sr = stats + row * row_step * P;
+    for (int p = j; p < P; p += 8) {
+      const float2 v = sr[p];
+      s += v.x;
+      ss += v.y;
+    }
+  }
+  s = group_sum<8>(s);
+  ss = group_sum<8>(ss);
+  if (row < M && j == 0) {
+    const float mean = s * inv_n;
+    const float var = ss * inv_n - mean * mean;
+    murstd[row] = make_float2(mean, rsqrtf(var + eps));
+  }
+}
+
 // the CHUNK (= H / 64) values the two templates are instantiated for; the
 // entry points reject every other H before they launch, so the switches
 // below need no default
@@ -175,6 +261,49 @@ bool has_chunk(int64_t H) {
 }
 
 }  // namespace
+
+bool cc::ln_h_supported(int64_t H) { return H == 128 || has_chunk(H); }
+
+extern "C" int cc_ln_stats_bf16(const void* x, int64_t M, int64_t H,
+                                void* stats, uint64_t stream) {
+  if (!x || !stats || M <= 0 || H <= 0)
+    return cc::set_error(CC_ERR_INVALID, "bad ln_stats args");
+  if (!cc::ln_h_supported(H))
+    return cc::set_error(CC_ERR_UNSUPPORTED, "unsupported H %lld", (long long)H);
+  dim3 block(256), grid((M + 3) / 4);
+  return cc::timed_launch("ln_stats", stream, [&] {
+    switch (H / 64) {
+      case 2:
+        hipLaunchKernelGGL(k_ln_stats_bf16_h128, grid, block, 0,
+                           (hipStream_t)stream, (const __bf16*)x,
+                           (float2*)stats, (long)M);
+        break;
+#define CASE(C)                                                            \
+  case C:                                                                  \
+    hipLaunchKernelGGL(k_ln_stats_bf16<C>, grid, block, 0,                 \
+                       (hipStream_t)stream, (const __bf16*)x,              \
+                       (float2*)stats, (long)M, (int)H);                   \
+    break;
+        CC_LN_CHUNKS(CASE)
+#undef CASE
+    }
+  });
+}
+
+extern "C" int cc_ln_finalize(const void* stats, int64_t M, int64_t H,
+                              int64_t row_step, float eps, void* murstd,
+                              uint64_t stream) {
+  if (!stats || !murstd || M <= 0 || H <= 0 || row_step <= 0)
+    return cc::set_error(CC_ERR_INVALID, "bad ln_finalize args");
+  if (!cc::ln_h_supported(H))
+    return cc::set_error(CC_ERR_UNSUPPORTED, "unsupported H %lld", (long long)H);
+  dim3 block(256), grid((M + 31) / 32);  // 8 lanes per row
+  return cc::timed_launch("ln_finalize", stream, [&] {
+    hipLaunchKernelGGL(k_ln_finalize, grid, block, 0, (hipStream_t)stream,
+                       (const float2*)stats, (float2*)murstd, (long)M,
+                       (int)(H / 64), (long)row_step, 1.0f / (float)H, eps);
+  });
+}
 
 extern "C" int cc_layernorm_bf16(const void* x, const void* w, const void* b,
                                  void* y, int64_t M, int64_t H, float eps,

@@ -142,6 +142,18 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.cc_layernorm_bf16.argtypes = [
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
         c.c_float, c.c_uint64]
+    lib.cc_ln_stats_bf16.argtypes = [
+        c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_uint64]
+    lib.cc_ln_finalize.argtypes = [
+        c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_float, c.c_void_p,
+        c.c_uint64]
+    lib.cc_gemm_bf16_res_stats.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64,
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64]
+    lib.cc_gemm_bf16_ln.argtypes = [
+        c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p,
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64,
+        c.c_int, c.c_float, c.c_uint64]
     lib.cc_embed_assemble_ln.argtypes = [
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
         c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_float, c.c_uint64]

@@ -26,7 +26,7 @@ import torch
 
 from cosmos_curate_amd import hotpath
 from cosmos_curate_amd.models import clip_weights as cw
-from cosmos_curate_amd.models.vit_encoder import VitEncoderAMD
+from cosmos_curate_amd.models.vit_encoder import VitEncoderAMD, cc_linear_ln
 
 
 class ClipVisionTowerAMD(VitEncoderAMD):
@@ -112,8 +112,12 @@ class ClipVisionTowerAMD(VitEncoderAMD):
             and (cfg.hidden // self.heads == 64 or not h.is_cuda)
         )
         if cls_only:
-            h = self._encode(h, n, seq, self.layers - 1)
-            cls_rows = self._last_layer_cls(h, self.layers - 1, n, seq)
+            stats = None
+            if self._folds(h):
+                h, stats = self._encode_folded(h, n, seq, self.layers - 1)
+            else:
+                h = self._encode(h, n, seq, self.layers - 1)
+            cls_rows = self._last_layer_cls(h, self.layers - 1, n, seq, stats)
         else:
             cls_rows = self._encode(h, n, seq)[:, 0]
         pooled = self._ln(cls_rows, self.post_ln_w, self.post_ln_b)
@@ -121,7 +125,8 @@ class ClipVisionTowerAMD(VitEncoderAMD):
         return emb / torch.linalg.vector_norm(emb, dim=-1, keepdim=True)
 
     def _last_layer_cls(
-        self, h: torch.Tensor, i: int, n: int, seq: int
+        self, h: torch.Tensor, i: int, n: int, seq: int,
+        stats: torch.Tensor | None = None,
     ) -> torch.Tensor:
         """Encoder layer ``i`` for the CLS rows only: (n, seq, H) -> (n, H).
 
@@ -132,15 +137,28 @@ class ClipVisionTowerAMD(VitEncoderAMD):
         the rows the full layer would have produced there.  The CLS rows
         of the LN1 output (A of the Q GEMM) and of ``h`` (residual of
         out-proj) are read in place through row strides.
+
+        With ``stats`` (the row statistics of ``h``, folded route) LN1 is
+        not run at all: the K/V GEMM and the Q GEMM read ``h`` itself, the
+        Q GEMM its CLS rows and their statistics at a row step of ``seq``.
+        LN2 at M = frames stays the LN kernel.
         """
         H = self.cfg.hidden
         hd = H // self.heads
         p = self._layer_params(i)
         w_qkv, b_qkv = p("w_qkv"), p("b_qkv")
-        y = self._ln(h, p("ln1_w"), p("ln1_b"))
         # rows ordered (q, k, v): contiguous slices, no weight copies
-        kv = self._linear(y.reshape(n * seq, H), w_qkv[H:], b_qkv[H:])
-        q = self._linear(y[:, 0], w_qkv[:H], b_qkv[:H])
+        if stats is not None:
+            wf, s, c = p("wf_qkv"), p("s_qkv"), p("c_qkv")
+            eps = self.cfg.ln_eps
+            hf = h.reshape(n * seq, H)
+            kv = cc_linear_ln(hf, stats, wf[H:], s[H:], c[H:], 0, eps)
+            q = cc_linear_ln(hf, stats, wf[:H], s[:H], c[:H], 0, eps,
+                             row_step=seq)
+        else:
+            y = self._ln(h, p("ln1_w"), p("ln1_b"))
+            kv = self._linear(y.reshape(n * seq, H), w_qkv[H:], b_qkv[H:])
+            q = self._linear(y[:, 0], w_qkv[:H], b_qkv[:H])
         if kv.is_cuda:
             lib = hotpath.require_gpu()
             attn = torch.empty((n, H), dtype=torch.bfloat16, device=kv.device)

@@ -14,7 +14,12 @@ key prefix; embeddings and pooling stay in the tower files.
 - attention is one cc_attn call straight off the QKV GEMM output
   (csrc/cc_attn.hip; the kernel for a sequence length is the library's
   choice, cc::attn_plan); head dims other than 64 take torch sdpa;
-- layernorms run the fused HIP kernel (f32 statistics);
+- LN1 and LN2 never materialise on the GPU: their affine part is folded
+  into the QKV / fc1 weights once at construction (fold_layernorm) and the
+  GEMM epilogue finishes the normalisation from per-row statistics that
+  the GEMM producing the residual stream wrote (DESIGN.md §14;
+  ``fold_ln = False`` restores the LN kernel + plain GEMM chain);
+- the remaining layernorms run the fused HIP kernel (f32 statistics);
 - activations are bf16 end-to-end.
 
 No CPU fallback: _linear() requires the HIP extension + a GPU (the tests
@@ -88,6 +93,96 @@ def cc_linear(
     return out
 
 
+def fold_layernorm(
+    w: torch.Tensor, b: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Fold a LayerNorm's affine part into the linear layer it feeds.
+
+    linear(layer_norm(x), w, b) = rstd * (W' x - mean * s) + c with
+    W' = bf16(w * gamma) per input column, s[n] = sum_k W'[n, k] and
+    c = w_bf16 @ beta + b.  ``s`` is the f32 value of the sum of the
+    ROUNDED W', the numbers the MFMA really multiplies: with any other sum
+    the row mean does not cancel.  Pure CPU arithmetic on the checkpoint;
+    returns (W' bf16, s f32, c f32).
+    """
+    w_fold = (w.float() * gamma.float()[None, :]).to(torch.bfloat16)
+    colsum = w_fold.double().sum(dim=1).float()
+    cbias = (w.to(torch.bfloat16).double() @ beta.double() + b.double()).float()
+    return w_fold.contiguous(), colsum.contiguous(), cbias.contiguous()
+
+
+def cc_ln_stats(x: torch.Tensor) -> torch.Tensor:
+    """Row statistics of x [M, H] bf16 as the folded GEMMs read them: f32
+    partial (sum, sum of squares) per 64-column block, [M, H/64, 2]."""
+    lib = hotpath.require_gpu()
+    assert x.dtype == torch.bfloat16 and x.is_contiguous()
+    M, H = x.shape
+    stats = torch.empty((M, H // 64, 2), dtype=torch.float32, device=x.device)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    hotpath.check(
+        lib.cc_ln_stats_bf16(x.data_ptr(), M, H, stats.data_ptr(), stream))
+    return stats
+
+
+def cc_linear_ln(
+    x: torch.Tensor,
+    stats: torch.Tensor,
+    w_fold: torch.Tensor,
+    colsum: torch.Tensor,
+    cbias: torch.Tensor,
+    act: int,
+    eps: float,
+    row_step: int = 1,
+) -> torch.Tensor:
+    """act(linear(layer_norm(x))) with the LayerNorm folded away
+    (cc_gemm_bf16_ln): x is the raw LN input, ``stats`` its row statistics,
+    (w_fold, colsum, cbias) from fold_layernorm.  ``row_step`` > 1 takes
+    every row_step-th row of x and of stats, in place."""
+    lib = hotpath.require_gpu()
+    assert x.dtype == torch.bfloat16 and x.is_contiguous()
+    assert w_fold.dtype == torch.bfloat16 and w_fold.is_contiguous()
+    rows, K = x.shape
+    assert stats.shape == (rows, K // 64, 2) and stats.is_contiguous()
+    M = (rows + row_step - 1) // row_step
+    N = w_fold.shape[0]
+    out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    murstd = torch.empty((M, 2), dtype=torch.float32, device=x.device)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    hotpath.check(
+        lib.cc_gemm_bf16_ln(
+            x.data_ptr(), row_step, stats.data_ptr(), murstd.data_ptr(),
+            w_fold.data_ptr(), colsum.data_ptr(), cbias.data_ptr(),
+            out.data_ptr(), M, N, K, act, eps, stream,
+        )
+    )
+    return out
+
+
+def cc_linear_res_stats(
+    x: torch.Tensor, w_bf16: torch.Tensor, bias_f32: torch.Tensor,
+    residual: torch.Tensor,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """(x @ w^T + bias + residual, its row statistics): cc_linear with a
+    residual whose epilogue also writes what cc_ln_stats would compute from
+    the output (cc_gemm_bf16_res_stats)."""
+    lib = hotpath.require_gpu()
+    assert x.dtype == torch.bfloat16 and x.is_contiguous()
+    assert residual.dtype == torch.bfloat16 and residual.is_contiguous()
+    M, K = x.shape
+    N = w_bf16.shape[0]
+    assert residual.shape == (M, N)
+    out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    stats = torch.empty((M, N // 64, 2), dtype=torch.float32, device=x.device)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    hotpath.check(
+        lib.cc_gemm_bf16_res_stats(
+            x.data_ptr(), w_bf16.data_ptr(), out.data_ptr(), M, N, K,
+            bias_f32.data_ptr(), residual.data_ptr(), stats.data_ptr(), stream,
+        )
+    )
+    return out, stats
+
+
 def _row_stride(t: torch.Tensor) -> int | None:
     """Row stride (elements) of a 2-D tensor the GEMM can read in place:
     unit column stride and rows that do not overlap; None otherwise."""
@@ -152,7 +247,14 @@ class VitEncoderAMD(torch.nn.Module):
     ``encoder.layers.``.  The patch-embed GEMM's K = 3*patch^2 is
     zero-padded to the kernel's 64-multiple requirement (588 -> 640 for
     L/14) — exact, the padded columns multiply zeros.
+
+    ``fold_ln`` (default True): on the GPU, LN1 and LN2 are folded into the
+    QKV and fc1 GEMMs (_layer_folded).  False runs the LN kernel and the
+    plain GEMMs — for A/B runs and parity tests; it is also what CPU
+    tensors and head dims other than 64 get.
     """
+
+    fold_ln = True
 
     def __init__(
         self, sd: dict[str, torch.Tensor], cfg: cw.VitConfig, prefix: str
@@ -190,6 +292,18 @@ class VitEncoderAMD(torch.nn.Module):
             reg(f"b_fc1_{i}", to_f32(sd[q + "mlp.fc1.bias"]))
             reg(f"w_fc2_{i}", to_bf(sd[q + "mlp.fc2.weight"]))
             reg(f"b_fc2_{i}", to_f32(sd[q + "mlp.fc2.bias"]))
+            # LN1 / LN2 folded into the GEMM they feed (derived, so kept
+            # out of the state dict); row order (q, k, v) as in w_qkv
+            for name, w, b, ln in (
+                ("qkv", torch.cat([sd[x + "weight"] for x in qkv], dim=0),
+                 getattr(self, f"b_qkv_{i}"), "ln1"),
+                ("fc1", sd[q + "mlp.fc1.weight"],
+                 getattr(self, f"b_fc1_{i}"), "ln2"),
+            ):
+                folded = fold_layernorm(
+                    w, b, getattr(self, f"{ln}_w_{i}"), getattr(self, f"{ln}_b_{i}"))
+                for pre, t in zip(("wf", "s", "c"), folded):
+                    reg(f"{pre}_{name}_{i}", t, persistent=False)
 
     # the one contraction primitive; tests may monkeypatch this
     def _linear(
@@ -271,10 +385,51 @@ class VitEncoderAMD(torch.nn.Module):
             y, p("w_fc2"), p("b_fc2"), residual=h.reshape(n * seq, H)
         ).reshape(n, seq, H)
 
+    def _folds(self, h: torch.Tensor) -> bool:
+        """Whether ``h`` takes the folded-LayerNorm route."""
+        return (
+            self.fold_ln and h.is_cuda
+            and self.cfg.hidden // self.heads == 64
+        )
+
+    def _layer_folded(
+        self, h: torch.Tensor, stats: torch.Tensor, i: int, n: int, seq: int
+    ) -> tuple[torch.Tensor, torch.Tensor]:
+        """Encoder layer ``i`` without LN kernels: (h (n*seq, H), its row
+        statistics) -> the same pair for the layer's output.  QKV and fc1
+        read the raw residual stream and normalise in their epilogue;
+        out-proj and fc2 write the statistics of what they store."""
+        p = self._layer_params(i)
+        eps = self.cfg.ln_eps
+        qkv_flat = cc_linear_ln(
+            h, stats, p("wf_qkv"), p("s_qkv"), p("c_qkv"), 0, eps)
+        attn = self._attention(qkv_flat, n, seq)
+        h, stats = cc_linear_res_stats(attn, p("w_out"), p("b_out"), h)
+        y = cc_linear_ln(
+            h, stats, p("wf_fc1"), p("s_fc1"), p("c_fc1"), self.act, eps)
+        return cc_linear_res_stats(y, p("w_fc2"), p("b_fc2"), h)
+
+    def _encode_folded(
+        self, h: torch.Tensor, n: int, seq: int, layers: int
+    ) -> tuple[torch.Tensor, torch.Tensor]:
+        """The first ``layers`` layers on the folded route: (n, seq, H) ->
+        ((n, seq, H), row statistics of the result).  One read-only pass
+        takes the statistics of the embedding; after that each layer's
+        GEMMs hand them on."""
+        H = self.cfg.hidden
+        h = h.reshape(n * seq, H)
+        stats = cc_ln_stats(h)
+        for i in range(layers):
+            h, stats = self._layer_folded(h, stats, i, n, seq)
+        return h.reshape(n, seq, H), stats
+
     def _encode(
         self, h: torch.Tensor, n: int, seq: int, layers: int | None = None
     ) -> torch.Tensor:
         """The first ``layers`` encoder layers (default: all of them)."""
-        for i in range(self.layers if layers is None else layers):
+        layers = self.layers if layers is None else layers
+        if self._folds(h):
+            return self._encode_folded(h, n, seq, layers)[0]
+        for i in range(layers):
             h = self._layer(h, i, n, seq)
         return h

@@ -345,6 +345,46 @@ int cc_attn_cls(const void* q, const void* k, const void* v, int64_t ldkv,
 int cc_layernorm_bf16(const void* x, const void* w, const void* b, void* y,
                       int64_t M, int64_t H, float eps, uint64_t stream);
 
+/* ---- LayerNorm folded into the GEMM that consumes it.
+ * With W' = W * gamma (per column k, rounded to bf16), s[n] = sum_k W'[n,k]
+ * (f32, of the rounded values) and c = W beta + b:
+ *   act(linear(layer_norm(x), W, b)) = act(rstd*(W' x - mean*s) + c)
+ * so the consuming GEMM reads the raw x and only needs (mean, rstd) per
+ * row.  Row statistics travel as f32 partial sums per 64-column block,
+ * stats [M, H/64, 2] = (sum x, sum x^2); no atomics, fixed summation
+ * order, bit-identical from run to run.  H as for cc_layernorm_bf16.
+ *
+ * cc_ln_stats_bf16: the partials of x [M, H] bf16, one read-only pass
+ * (timed as "ln_stats").
+ * cc_ln_finalize: murstd[r] = (mean, rstd) [M, 2] f32 from the partials of
+ * stats row r*row_step; var = sum x^2/H - mean^2, rstd = rsqrt(var + eps),
+ * cc_layernorm_bf16's form (timed as "ln_finalize").
+ * cc_gemm_bf16_res_stats: cc_gemm_bf16_ex(A, B, C, ..., bias, bf16 out,
+ * act 0, residual) — C bit-identical to it — that also writes the
+ * partials of the C rows it stores, stats [M, N/64, 2].  bias and residual
+ * required.  The 256-tile body takes them in its epilogue; where the plan
+ * picks the 128-tile body the entry runs the stats kernel on C afterwards.
+ * cc_gemm_bf16_ln: C [M,N] bf16 = act(rstd*(A Wfold^T - mean*colsum) +
+ * cbias).  A row i starts at A + i*row_step*K and its statistics are stats
+ * row i*row_step (row_step 1 = dense; > 1 reads e.g. the CLS rows of a
+ * [frames*seq, K] tensor in place, on the 128-tile body).  murstd is
+ * [M, 2] f32 scratch the call fills (cc_ln_finalize) and reads.  Timed as
+ * "gemm_bf16" plus "ln_finalize".
+ * All: CC_ERR_INVALID on null pointers or non-positive sizes,
+ * CC_ERR_UNSUPPORTED on a width without LayerNorm kernels, before any
+ * launch. */
+int cc_ln_stats_bf16(const void* x, int64_t M, int64_t H, void* stats,
+                     uint64_t stream);
+int cc_ln_finalize(const void* stats, int64_t M, int64_t H, int64_t row_step,
+                   float eps, void* murstd, uint64_t stream);
+int cc_gemm_bf16_res_stats(const void* A, const void* B, void* C, int64_t M,
+                           int64_t N, int64_t K, const float* bias,
+                           const void* residual, void* stats, uint64_t stream);
+int cc_gemm_bf16_ln(const void* A, int64_t row_step, const void* stats,
+                    void* murstd, const void* Wfold, const float* colsum,
+                    const float* cbias, void* C, int64_t M, int64_t N,
+                    int64_t K, int act, float eps, uint64_t stream);
+
 /* ---- fused ViT embedding assembly: out[f*tokens + t] =
  * LayerNorm( (t==0 ? cls : tok[f*(tokens-1)+t-1]) + pos[t] ).
  * Replaces the HF CLIPVisionEmbeddings cat + position-embedding add +
