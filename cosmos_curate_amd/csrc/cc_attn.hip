@@ -10,11 +10,29 @@
 //                 measured slower here;
 //   k_attn_mid    (ViT-L/14's 257, SigLIP-L16-256's 256): Q/K fragments
 //                 direct from global (16B-contiguous rows), LDS only
-//                 V^T + P -> 2 WG/CU;
-//   k_attn_flash  (SigLIP-384-class): K/V streamed in 64-row tiles with
-//                 online softmax, O rescaled flash-style.
-// Plus k_attn_cls (any seq): one query row per (frame, head) for the
-// last layer of a CLS-pooled tower — separate q, strided K/V, O [n, H].
+//                 V^T + P -> 2 WG/CU at head dim 64, 1 above;
+//   k_attn_flash  (SigLIP-384-class; above head dim 64 also most of
+//                 65..288, e.g. SigLIP-so400m-224's 256 at head dim 72):
+//                 K/V streamed in 64-row tiles with online softmax, O
+//                 rescaled flash-style.
+// Plus k_attn_cls (any seq, head dim 64): one query row per (frame, head)
+// for the last layer of a CLS-pooled tower — separate q, strided K/V,
+// O [n, H].
+//
+// Head dim: each rung is a template on HD, instantiated for every
+// multiple of 8 in [64, 128] (so400m 72, ViT-H 80, ViT-g 88, bigG 104,
+// ...).  The MFMA shapes pad it: QK^T runs ceil(HD/32) 16x16x32 k-steps,
+// PV ceil(HD/16) column fragments.  Nothing past column HD of a head is
+// ever read or written — those addresses are the next head, the next
+// Q/K/V section, the next row or past the buffer:
+//   - a fragment chunk is 8 elements at a multiple of 8, so with
+//     HD % 8 == 0 it lies wholly inside or wholly outside [0, HD); an
+//     outside chunk is a zero register (both operands, so the pad
+//     contributes exactly 0 to every score), never a load;
+//   - V^T rows >= HD are written as zeros; they feed only output columns
+//     >= HD, which are never stored.
+// Head offsets are multiples of 16 bytes for every such HD, which keeps
+// the bf16x8 loads legal.  At HD = 64 every pad predicate folds away.
 //
 // Numerics (all rungs): f32 accumulation and softmax (matches sdpa's
 // f32 softmax on bf16 inputs); probabilities round to bf16 before PV,
@@ -35,8 +53,19 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int SMAX = cc::ATTN_SMALL_MAX;  // padded sequence tile
-constexpr int HD = cc::ATTN_HD;           // head dim
 constexpr int LD = 72;     // LDS row stride (pad 8 elements vs 64 banks)
+
+// What the MFMA shapes make of a head dim.
+template <int HD>
+struct HeadDim {
+  static_assert(cc::attn_hd_supported(HD), "head dim outside the ladder");
+  static constexpr int HDK = (HD + 31) / 32 * 32;  // QK^T k extent (k-steps of 32)
+  static constexpr int NF = (HD + 15) / 16;        // PV column fragments
+  static constexpr int HDV = NF * 16;              // V^T rows held in LDS
+  // staging passes: a pass covers 64 head columns, thread t -> row t>>2,
+  // columns 64*pass + 16*(t&3) .. +15
+  static constexpr int NPASS = (HD + 63) / 64;
+};
 
 // NOTE: the direct-global Q/K variant (4 WG/CU) was tried here too and
 // measured SLOWER (89 -> 126 us/launch, profiles/r01_rocprof_b32_afterfusions.txt)
@@ -44,20 +73,24 @@ constexpr int LD = 72;     // LDS row stride (pad 8 elements vs 64 banks)
 // per wave costs more than the staging saves (guide rule 7); the
 // LDS-resident form below stays.  k_attn_mid (seq 257) keeps the
 // direct-global form where it measured FASTER (L/14 step 80.3 -> 75.1 ms).
+template <int HD>
 __global__ __launch_bounds__(256, 2) void k_attn_small(
     const __bf16* __restrict__ qkv, __bf16* __restrict__ out, long n_frames,
     int seq, int heads, int hidden, float scale) {
+  using G = HeadDim<HD>;
+  constexpr int LDQ = G::HDK + 8;  // Q / K row stride (72 at HD 64)
   // one workgroup per (frame, head)
   const long fh = blockIdx.x;
   const long frame = fh / heads;
   const int head = fh % heads;
   if (frame >= n_frames) return;
 
-  __shared__ __bf16 lds[4 * SMAX * LD];  // Q, K, Vt, P
+  // Q, K [SMAX][LDQ] (columns [HD, HDK) zero), Vt [HDV][LD], P [SMAX][LD]
+  __shared__ __bf16 lds[2 * SMAX * LDQ + (G::HDV + SMAX) * LD];
   __bf16* Q = lds;
-  __bf16* K = lds + SMAX * LD;
-  __bf16* Vt = lds + 2 * SMAX * LD;
-  __bf16* P = lds + 3 * SMAX * LD;
+  __bf16* K = lds + SMAX * LDQ;
+  __bf16* Vt = lds + 2 * SMAX * LDQ;
+  __bf16* P = Vt + G::HDV * LD;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -78,15 +111,49 @@ __global__ __launch_bounds__(256, 2) void k_attn_small(
       v0 = *(const bf16x8*)(qkv + base + 2 * hidden + d0);
       v1 = *(const bf16x8*)(qkv + base + 2 * hidden + d0 + 8);
     }
-    *(bf16x8*)(Q + row * LD + d0) = q0;
-    *(bf16x8*)(Q + row * LD + d0 + 8) = q1;
-    *(bf16x8*)(K + row * LD + d0) = k0;
-    *(bf16x8*)(K + row * LD + d0 + 8) = k1;
+    *(bf16x8*)(Q + row * LDQ + d0) = q0;
+    *(bf16x8*)(Q + row * LDQ + d0 + 8) = q1;
+    *(bf16x8*)(K + row * LDQ + d0) = k0;
+    *(bf16x8*)(K + row * LDQ + d0 + 8) = k1;
     // V transposed: Vt[d][row] = V[row][d]
 #pragma unroll
     for (int e = 0; e < 8; e++) {
       Vt[(d0 + e) * LD + row] = v0[e];
       Vt[(d0 + 8 + e) * LD + row] = v1[e];
+    }
+  }
+  // ---- head dims above 64: columns 64 + (t&3)*16.. of the same row.  A
+  // chunk inside the head is loaded, one outside stays zero; d0 % 16 == 0,
+  // so both chunks lie on one side of HDK (Q/K extent) and of HDV (Vt
+  // rows) ----
+  if constexpr (HD > 64) {
+    const int row = tid >> 2;
+    const int d0 = 64 + (tid & 3) * 16;
+    const long base = ((frame * seq + row) * 3) * (long)hidden + (long)head * HD;
+    bf16x8 z = {};
+    bf16x8 q0 = z, q1 = z, k0 = z, k1 = z, v0 = z, v1 = z;
+    if (row < seq && d0 < HD) {
+      q0 = *(const bf16x8*)(qkv + base + d0);
+      k0 = *(const bf16x8*)(qkv + base + hidden + d0);
+      v0 = *(const bf16x8*)(qkv + base + 2 * hidden + d0);
+    }
+    if (row < seq && d0 + 8 < HD) {
+      q1 = *(const bf16x8*)(qkv + base + d0 + 8);
+      k1 = *(const bf16x8*)(qkv + base + hidden + d0 + 8);
+      v1 = *(const bf16x8*)(qkv + base + 2 * hidden + d0 + 8);
+    }
+    if (d0 < G::HDK) {
+      *(bf16x8*)(Q + row * LDQ + d0) = q0;
+      *(bf16x8*)(Q + row * LDQ + d0 + 8) = q1;
+      *(bf16x8*)(K + row * LDQ + d0) = k0;
+      *(bf16x8*)(K + row * LDQ + d0 + 8) = k1;
+    }
+    if (d0 < G::HDV) {
+#pragma unroll
+      for (int e = 0; e < 8; e++) {
+        Vt[(d0 + e) * LD + row] = v0[e];
+        Vt[(d0 + 8 + e) * LD + row] = v1[e];
+      }
     }
   }
   __syncthreads();
@@ -97,11 +164,11 @@ __global__ __launch_bounds__(256, 2) void k_attn_small(
     const int qrow = 16 * wid + (lane & 15);
     const int k0e = 8 * (lane >> 4);
 #pragma unroll
-    for (int kk = 0; kk < HD; kk += 32) {
-      bf16x8 qf = *(const bf16x8*)(Q + qrow * LD + kk + k0e);
+    for (int kk = 0; kk < G::HDK; kk += 32) {
+      bf16x8 qf = *(const bf16x8*)(Q + qrow * LDQ + kk + k0e);
 #pragma unroll
       for (int n = 0; n < 4; n++) {
-        bf16x8 kf = *(const bf16x8*)(K + (n * 16 + (lane & 15)) * LD + kk + k0e);
+        bf16x8 kf = *(const bf16x8*)(K + (n * 16 + (lane & 15)) * LDQ + kk + k0e);
         acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, kf, acc[n], 0, 0, 0);
       }
     }
@@ -153,8 +220,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_small(
   }
   __syncthreads();
 
-  // ---- O = P Vt^T : rows [16w,16w+16) of O, cols d = 0..63 ----
-  f32x4 oacc[4] = {};
+  // ---- O = P Vt^T : rows [16w,16w+16) of O, cols d = 0..HDV-1 ----
+  f32x4 oacc[G::NF] = {};
   {
     const int prow = 16 * wid + (lane & 15);
     const int j0 = 8 * (lane >> 4);
@@ -162,22 +229,23 @@ __global__ __launch_bounds__(256, 2) void k_attn_small(
     for (int kk = 0; kk < SMAX; kk += 32) {
       bf16x8 pf = *(const bf16x8*)(P + prow * LD + kk + j0);
 #pragma unroll
-      for (int n = 0; n < 4; n++) {
+      for (int n = 0; n < G::NF; n++) {
         bf16x8 vf = *(const bf16x8*)(Vt + (n * 16 + (lane & 15)) * LD + kk + j0);
         oacc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vf, oacc[n], 0, 0, 0);
       }
     }
   }
-  // ---- store O: (row = 16w + (lane>>4)*4 + reg, d = n*16 + lane&15) ----
+  // ---- store O: (row = 16w + (lane>>4)*4 + reg, d = n*16 + lane&15);
+  // columns >= HD of the last fragment belong to the next head ----
   {
     const int dcol = lane & 15;
     const int rbase = 16 * wid + 4 * (lane >> 4);
 #pragma unroll
-    for (int nn = 0; nn < 4; nn++)
+    for (int nn = 0; nn < G::NF; nn++)
 #pragma unroll
       for (int reg = 0; reg < 4; reg++) {
         const int row = rbase + reg;
-        if (row < seq)
+        if (row < seq && (nn * 16 + 16 <= HD || nn * 16 + dcol < HD))
           out[(frame * seq + row) * (long)hidden + head * HD + nn * 16 + dcol] =
               (__bf16)oacc[nn][reg];
       }
@@ -192,21 +260,26 @@ __global__ __launch_bounds__(256, 2) void k_attn_small(
 // image for the PV matmul) and P live in LDS: 74 KB -> 2 WG/CU, which
 // doubles the waves/SIMD vs the LDS-everything form (measured 621 us
 // -> see profiles/r01_attn_mid2; the LDS-everything form capped at
-// ~204 TF with 1 wave/SIMD).
+// ~204 TF with 1 wave/SIMD).  Above head dim 64 the V^T image grows
+// past half the CU's LDS and one workgroup per CU runs; the plan then
+// keeps this rung only where it still measured faster than flash
+// (cc_attn_plan.hpp has the numbers).
 constexpr int SMID = cc::ATTN_MID_MAX;  // padded sequence (18 x 16-col frags)
 constexpr int LDM = SMID + 8;   // LDS s-stride for Vt / P rows
 
+template <int HD>
 __global__ __launch_bounds__(256, 2) void k_attn_mid(
     const __bf16* __restrict__ qkv, __bf16* __restrict__ out, long n_frames,
     int seq, int heads, int hidden, float scale) {
+  using G = HeadDim<HD>;
   const long fh = blockIdx.x;
   const long frame = fh / heads;
   const int head = fh % heads;
   if (frame >= n_frames) return;
 
-  __shared__ __bf16 lds[2 * 64 * LDM];
-  __bf16* Vt = lds;              // [64][LDM] rows d, cols s
-  __bf16* P = lds + 64 * LDM;    // [64][LDM] rows q, cols s
+  __shared__ __bf16 lds[(G::HDV + 64) * LDM];
+  __bf16* Vt = lds;                  // [HDV][LDM] rows d, cols s
+  __bf16* P = lds + G::HDV * LDM;    // [64][LDM] rows q, cols s
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -235,6 +308,31 @@ __global__ __launch_bounds__(256, 2) void k_attn_mid(
       }
     }
   }
+  // ---- head dims above 64: d 64 + (t&3)*16.. of the same rows; chunks
+  // past HD are zero rows of V^T, rows past HDV are not held
+  if constexpr (HD > 64) {
+    const int row = tid >> 2;
+    const int d0 = 64 + (tid & 3) * 16;
+    if (d0 < G::HDV) {
+#pragma unroll
+      for (int j = 0; j < SMID / 64 + 1; j++) {
+        const int r = j * 64 + row;
+        if (r >= SMID) break;
+        bf16x8 z = {};
+        bf16x8 v0 = z, v1 = z;
+        if (r < seq) {
+          const long base = qkv_base + (long)r * 3 * hidden + 2 * hidden;
+          if (d0 < HD) v0 = *(const bf16x8*)(qkv + base + d0);
+          if (d0 + 8 < HD) v1 = *(const bf16x8*)(qkv + base + d0 + 8);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          Vt[(d0 + e) * LDM + r] = v0[e];
+          Vt[(d0 + 8 + e) * LDM + r] = v1[e];
+        }
+      }
+    }
+  }
 
   const int n_qtiles = (seq + 63) / 64;
   for (int qt = 0; qt < n_qtiles; qt++) {
@@ -243,7 +341,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_mid(
 
     // ---- S = Q K^T: wave rows [16*wid, +16), 18 col frags; Q/K frags
     // read directly from global (16B contiguous), rows clamped to seq-1
-    // (masked in softmax anyway).
+    // (masked in softmax anyway); chunks past HD are zero, not loaded.
     f32x4 acc[SMID / 16];
 #pragma unroll
     for (int n = 0; n < SMID / 16; n++) acc[n] = f32x4{};
@@ -252,15 +350,20 @@ __global__ __launch_bounds__(256, 2) void k_attn_mid(
       qrow = qrow < seq ? qrow : seq - 1;
       const int k0e = 8 * (lane >> 4);
 #pragma unroll
-      for (int kk = 0; kk < HD; kk += 32) {
-        bf16x8 qf =
-            *(const bf16x8*)(qkv + qkv_base + (long)qrow * 3 * hidden + kk + k0e);
+      for (int kk = 0; kk < G::HDK; kk += 32) {
+        const bool in = kk + 32 <= HD || kk + k0e < HD;
+        bf16x8 qf = {};
+        if (in)
+          qf = *(const bf16x8*)(qkv + qkv_base + (long)qrow * 3 * hidden + kk +
+                                k0e);
 #pragma unroll
         for (int n = 0; n < SMID / 16; n++) {
           int krow = n * 16 + (lane & 15);
           krow = krow < seq ? krow : seq - 1;
-          bf16x8 kf = *(const bf16x8*)(qkv + qkv_base + (long)krow * 3 * hidden +
-                                       hidden + kk + k0e);
+          bf16x8 kf = {};
+          if (in)
+            kf = *(const bf16x8*)(qkv + qkv_base + (long)krow * 3 * hidden +
+                                  hidden + kk + k0e);
           acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, kf, acc[n], 0, 0, 0);
         }
       }
@@ -310,8 +413,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_mid(
     }
     __syncthreads();
 
-    // ---- O = P V : rows [16*wid,+16), d cols 0..63
-    f32x4 oacc[4] = {};
+    // ---- O = P V : rows [16*wid,+16), d cols 0..HDV-1
+    f32x4 oacc[G::NF] = {};
     {
       const int prow = 16 * wid + (lane & 15);
       const int j0 = 8 * (lane >> 4);
@@ -319,7 +422,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_mid(
       for (int kk = 0; kk < SMID; kk += 32) {
         bf16x8 pf = *(const bf16x8*)(P + prow * LDM + kk + j0);
 #pragma unroll
-        for (int n = 0; n < 4; n++) {
+        for (int n = 0; n < G::NF; n++) {
           bf16x8 vf =
               *(const bf16x8*)(Vt + (n * 16 + (lane & 15)) * LDM + kk + j0);
           oacc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vf, oacc[n], 0, 0, 0);
@@ -330,11 +433,11 @@ __global__ __launch_bounds__(256, 2) void k_attn_mid(
       const int dcol = lane & 15;
       const int rbase = 16 * wid + 4 * (lane >> 4);
 #pragma unroll
-      for (int nn = 0; nn < 4; nn++)
+      for (int nn = 0; nn < G::NF; nn++)
 #pragma unroll
         for (int reg = 0; reg < 4; reg++) {
           const int row = q0 + rbase + reg;
-          if (row < seq)
+          if (row < seq && (nn * 16 + 16 <= HD || nn * 16 + dcol < HD))
             out[(frame * seq + row) * (long)hidden + head * HD + nn * 16 +
                 dcol] = (__bf16)oacc[nn][reg];
         }
@@ -348,16 +451,19 @@ __global__ __launch_bounds__(256, 2) void k_attn_mid(
 // One workgroup per (frame, head, q-tile of 64 rows); Q and K fragments
 // load straight from global (16B-contiguous in the fused-QKV layout,
 // same trick as k_attn_mid); per KV-tile, V^T and the probability tile
-// stage through a small LDS image (~19 KB -> high occupancy).  f32
+// stage through a small LDS image (~19 KB at head dim 64, ~28 KB at 128
+// -> high occupancy).  f32
 // running max/sum per row, O accumulators rescaled flash-style,
 // probabilities rounded to bf16 before PV (same numerics contract as
 // the resident kernels).
 constexpr int FKV = 64;        // kv tile rows
 constexpr int LDF = FKV + 8;   // LDS s-stride
 
+template <int HD>
 __global__ __launch_bounds__(256, 2) void k_attn_flash(
     const __bf16* __restrict__ qkv, __bf16* __restrict__ out, long n_frames,
     int seq, int heads, int hidden, float scale) {
+  using G = HeadDim<HD>;
   const int n_qtiles = (seq + 63) / 64;
   const long fhq = blockIdx.x;
   const int qt = (int)(fhq % n_qtiles);
@@ -366,9 +472,9 @@ __global__ __launch_bounds__(256, 2) void k_attn_flash(
   const int head = fh % heads;
   if (frame >= n_frames) return;
 
-  __shared__ __bf16 lds[2 * 64 * LDF];
-  __bf16* Vt = lds;              // [64 d][LDF s]
-  __bf16* P = lds + 64 * LDF;    // [64 q][LDF s]
+  __shared__ __bf16 lds[(G::HDV + 64) * LDF];
+  __bf16* Vt = lds;                  // [HDV d][LDF s]
+  __bf16* P = lds + G::HDV * LDF;    // [64 q][LDF s]
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -379,7 +485,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_flash(
   // per-lane row state (rows rbase..rbase+3 of this wave's 16)
   const int rbase_l = 4 * (lane >> 4);
   float m_run[4], l_run[4];
-  f32x4 oacc[4] = {};
+  f32x4 oacc[G::NF] = {};
 #pragma unroll
   for (int r = 0; r < 4; r++) {
     m_run[r] = -1e30f;
@@ -389,17 +495,21 @@ __global__ __launch_bounds__(256, 2) void k_attn_flash(
   const int n_kv = (seq + FKV - 1) / FKV;
   for (int kt = 0; kt < n_kv; kt++) {
     const int k0 = kt * FKV;
-    // ---- V^T tile into LDS (thread t -> row t>>2, d (t&3)*16)
+    // ---- V^T tile into LDS (thread t -> row t>>2, d (t&3)*16, +64 per
+    // head-dim pass; chunks past HD are zero rows of V^T)
     __syncthreads();  // P/Vt free from the previous tile
-    {
+#pragma unroll
+    for (int ps = 0; ps < G::NPASS; ps++) {
       const int row = tid >> 2;
-      const int d0 = (tid & 3) * 16;
+      const int d0 = (tid & 3) * 16 + 64 * ps;
+      if (d0 >= G::HDV) continue;
+      const bool in0 = d0 < HD, in1 = d0 + 8 < HD;
       bf16x8 z = {};
       bf16x8 v0 = z, v1 = z;
       if (k0 + row < seq) {
         const long base = qkv_base + (long)(k0 + row) * 3 * hidden + 2 * hidden;
-        v0 = *(const bf16x8*)(qkv + base + d0);
-        v1 = *(const bf16x8*)(qkv + base + d0 + 8);
+        if (in0) v0 = *(const bf16x8*)(qkv + base + d0);
+        if (in1) v1 = *(const bf16x8*)(qkv + base + d0 + 8);
       }
 #pragma unroll
       for (int e = 0; e < 8; e++) {
@@ -408,22 +518,28 @@ __global__ __launch_bounds__(256, 2) void k_attn_flash(
       }
     }
 
-    // ---- S tile = Q K^T (wave rows, 4 col frags), direct global Q/K
+    // ---- S tile = Q K^T (wave rows, 4 col frags), direct global Q/K;
+    // chunks past HD are zero, not loaded
     f32x4 acc[4] = {};
     {
       int qrow = q0 + 16 * wid + (lane & 15);
       qrow = qrow < seq ? qrow : seq - 1;
       const int k0e = 8 * (lane >> 4);
 #pragma unroll
-      for (int kk = 0; kk < HD; kk += 32) {
-        bf16x8 qf =
-            *(const bf16x8*)(qkv + qkv_base + (long)qrow * 3 * hidden + kk + k0e);
+      for (int kk = 0; kk < G::HDK; kk += 32) {
+        const bool in = kk + 32 <= HD || kk + k0e < HD;
+        bf16x8 qf = {};
+        if (in)
+          qf = *(const bf16x8*)(qkv + qkv_base + (long)qrow * 3 * hidden + kk +
+                                k0e);
 #pragma unroll
         for (int n = 0; n < 4; n++) {
           int krow = k0 + n * 16 + (lane & 15);
           krow = krow < seq ? krow : seq - 1;
-          bf16x8 kf = *(const bf16x8*)(qkv + qkv_base + (long)krow * 3 * hidden +
-                                       hidden + kk + k0e);
+          bf16x8 kf = {};
+          if (in)
+            kf = *(const bf16x8*)(qkv + qkv_base + (long)krow * 3 * hidden +
+                                  hidden + kk + k0e);
           acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, kf, acc[n], 0, 0, 0);
         }
       }
@@ -477,7 +593,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_flash(
     __syncthreads();
 
     // ---- O = alpha * O + P V
-    f32x4 pv[4] = {};
+    f32x4 pv[G::NF] = {};
     {
       const int prow = 16 * wid + (lane & 15);
       const int j0 = 8 * (lane >> 4);
@@ -485,7 +601,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_flash(
       for (int kk = 0; kk < FKV; kk += 32) {
         bf16x8 pf = *(const bf16x8*)(P + prow * LDF + kk + j0);
 #pragma unroll
-        for (int n = 0; n < 4; n++) {
+        for (int n = 0; n < G::NF; n++) {
           bf16x8 vf =
               *(const bf16x8*)(Vt + (n * 16 + (lane & 15)) * LDF + kk + j0);
           pv[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vf, pv[n], 0, 0, 0);
@@ -493,22 +609,22 @@ __global__ __launch_bounds__(256, 2) void k_attn_flash(
       }
     }
 #pragma unroll
-    for (int n = 0; n < 4; n++)
+    for (int n = 0; n < G::NF; n++)
 #pragma unroll
       for (int reg = 0; reg < 4; reg++)
         oacc[n][reg] = oacc[n][reg] * alpha[reg] + pv[n][reg];
   }
 
-  // ---- store O / l
+  // ---- store O / l (columns >= HD of the last fragment: next head's)
   {
     const int dcol = lane & 15;
     const int rb = 16 * wid + rbase_l;
 #pragma unroll
-    for (int nn = 0; nn < 4; nn++)
+    for (int nn = 0; nn < G::NF; nn++)
 #pragma unroll
       for (int reg = 0; reg < 4; reg++) {
         const int row = q0 + rb + reg;
-        if (row < seq)
+        if (row < seq && (nn * 16 + 16 <= HD || nn * 16 + dcol < HD))
           out[(frame * seq + row) * (long)hidden + head * HD + nn * 16 + dcol] =
               (__bf16)(oacc[nn][reg] / l_run[reg]);
       }
@@ -533,6 +649,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_flash(
 // unnormalized probabilities rounded to bf16 before PV, O / l at the
 // end); the cross-lane reductions run in a fixed order, no atomics ->
 // bit-identical from run to run.
+constexpr int CLS_HD = cc::ATTN_CLS_HD;
+
 __global__ __launch_bounds__(256) void k_attn_cls(
     const __bf16* __restrict__ q, const __bf16* __restrict__ k,
     const __bf16* __restrict__ v, long ldkv, __bf16* __restrict__ out,
@@ -548,11 +666,11 @@ __global__ __launch_bounds__(256) void k_attn_cls(
   float qf[8];
   {
     const bf16x8 q8 =
-        *(const bf16x8*)(q + frame * (long)hidden + head * HD + dg * 8);
+        *(const bf16x8*)(q + frame * (long)hidden + head * CLS_HD + dg * 8);
 #pragma unroll
     for (int e = 0; e < 8; e++) qf[e] = (float)q8[e] * scale;
   }
-  const long kv_base = frame * (long)seq * ldkv + (long)head * HD + dg * 8;
+  const long kv_base = frame * (long)seq * ldkv + (long)head * CLS_HD + dg * 8;
 
   float m_run = -1e30f, l_run = 0.0f;
   float oacc[8] = {};
@@ -620,7 +738,7 @@ __global__ __launch_bounds__(256) void k_attn_cls(
     bf16x8 o8;
 #pragma unroll
     for (int d = 0; d < 8; d++) o8[d] = (__bf16)(oacc[d] * inv);
-    *(bf16x8*)(out + frame * (long)hidden + head * HD + dg * 8) = o8;
+    *(bf16x8*)(out + frame * (long)hidden + head * CLS_HD + dg * 8) = o8;
   }
 }
 
@@ -632,7 +750,7 @@ extern "C" int cc_attn_cls(const void* q, const void* k, const void* v,
                            uint64_t stream) {
   if (!q || !k || !v || !out || n_frames <= 0 || seq <= 0 || heads <= 0)
     return cc::set_error(CC_ERR_INVALID, "bad attn_cls args");
-  if (hidden != heads * HD)
+  if (hidden != heads * CLS_HD)
     return cc::set_error(CC_ERR_UNSUPPORTED, "cc_attn_cls needs hd == 64");
   // 16-byte row loads: stride and bases must keep every row 16B-aligned
   if (ldkv < hidden || ldkv % 8 != 0 || ((uintptr_t)q & 15) ||
@@ -656,35 +774,46 @@ namespace {
 
 using AttnKernel = void (*)(const __bf16*, __bf16*, long, int, int, int,
                             float);
-struct AttnRung {
-  const char* label;  // timing name
-  AttnKernel kernel;
+// timing names, indexed by cc_attn_plan_info.rung
+constexpr const char* kAttnLabels[3] = {"attn_small", "attn_mid",
+                                        "attn_flash"};
+// the head dims cc::attn_hd_supported accepts, in order
+#define CC_ATTN_HDS(X) X(64) X(72) X(80) X(88) X(96) X(104) X(112) X(120) X(128)
+// [(hd - ATTN_HD_MIN) / ATTN_HD_STEP][rung]
+constexpr AttnKernel kAttnKernels[][3] = {
+#define ROW(H) {k_attn_small<H>, k_attn_mid<H>, k_attn_flash<H>},
+    CC_ATTN_HDS(ROW)
+#undef ROW
 };
-constexpr AttnRung kAttnRungs[3] = {  // indexed by cc_attn_plan_info.rung
-    {"attn_small", k_attn_small},
-    {"attn_mid", k_attn_mid},
-    {"attn_flash", k_attn_flash}};
+static_assert(sizeof(kAttnKernels) / sizeof(kAttnKernels[0]) ==
+                  (cc::ATTN_HD_MAX - cc::ATTN_HD_MIN) / cc::ATTN_HD_STEP + 1,
+              "one kernel row per supported head dim");
 
 // The one launcher: runs what cc::attn_plan says.  `only` >= 0 (the rung
-// entries) additionally requires the plan to land on that rung.
-int attn_launch(int only, const void* qkv, void* out, int64_t n_frames,
-                int seq, int heads, int hidden, float scale,
+// entries) additionally requires the plan to land on that rung; `force`
+// >= 0 (cc_attn_rung) makes the plan take that rung.
+int attn_launch(int only, int force, const void* qkv, void* out,
+                int64_t n_frames, int seq, int heads, int hidden, float scale,
                 uint64_t stream) {
   if (!qkv || !out) return cc::set_error(CC_ERR_INVALID, "bad attn args");
-  // 16-byte row loads: rows are 16B multiples at hd == 64, bases must be too
+  // 16-byte row loads: rows and head offsets are 16B multiples at
+  // hd % 8 == 0, bases must be too
   if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15))
     return cc::set_error(CC_ERR_INVALID,
                          "cc_attn needs 16-byte aligned qkv/out");
   cc_attn_plan_info plan;
-  if (int rc = cc::attn_plan(n_frames, seq, heads, hidden, &plan)) return rc;
-  const AttnRung& rung = kAttnRungs[plan.rung];
+  if (int rc = cc::attn_plan(n_frames, seq, heads, hidden, &plan, force))
+    return rc;
   if (only >= 0 && only != plan.rung)
     return cc::set_error(CC_ERR_UNSUPPORTED,
                          "cc_%s does not cover seq %d, which runs %s (cc_attn "
                          "picks the rung)",
-                         kAttnRungs[only].label, seq, rung.label);
-  return cc::timed_launch(rung.label, stream, [&] {
-    hipLaunchKernelGGL(rung.kernel, dim3(plan.grid), dim3(plan.block), 0,
+                         kAttnLabels[only], seq, kAttnLabels[plan.rung]);
+  const AttnKernel kernel =
+      kAttnKernels[(hidden / heads - cc::ATTN_HD_MIN) / cc::ATTN_HD_STEP]
+                  [plan.rung];
+  return cc::timed_launch(kAttnLabels[plan.rung], stream, [&] {
+    hipLaunchKernelGGL(kernel, dim3(plan.grid), dim3(plan.block), 0,
                        (hipStream_t)stream, (const __bf16*)qkv, (__bf16*)out,
                        (long)n_frames, seq, heads, hidden, scale);
   });
@@ -700,28 +829,36 @@ extern "C" int cc_attn_plan(int64_t n_frames, int seq, int heads, int hidden,
 
 extern "C" int cc_attn(const void* qkv, void* out, int64_t n_frames, int seq,
                        int heads, int hidden, float scale, uint64_t stream) {
-  return attn_launch(-1, qkv, out, n_frames, seq, heads, hidden, scale,
+  return attn_launch(-1, -1, qkv, out, n_frames, seq, heads, hidden, scale,
                      stream);
 }
 
 extern "C" int cc_attn_small(const void* qkv, void* out, int64_t n_frames,
                              int seq, int heads, int hidden, float scale,
                              uint64_t stream) {
-  return attn_launch(CC_ATTN_SMALL, qkv, out, n_frames, seq, heads, hidden,
+  return attn_launch(CC_ATTN_SMALL, -1, qkv, out, n_frames, seq, heads, hidden,
                      scale, stream);
 }
 
 extern "C" int cc_attn_mid(const void* qkv, void* out, int64_t n_frames,
                            int seq, int heads, int hidden, float scale,
                            uint64_t stream) {
-  return attn_launch(CC_ATTN_MID, qkv, out, n_frames, seq, heads, hidden,
+  return attn_launch(CC_ATTN_MID, -1, qkv, out, n_frames, seq, heads, hidden,
                      scale, stream);
 }
 
 extern "C" int cc_attn_flash(const void* qkv, void* out, int64_t n_frames,
                              int seq, int heads, int hidden, float scale,
                              uint64_t stream) {
-  return attn_launch(CC_ATTN_FLASH, qkv, out, n_frames, seq, heads, hidden,
+  return attn_launch(CC_ATTN_FLASH, -1, qkv, out, n_frames, seq, heads, hidden,
                      scale, stream);
 }
 
+extern "C" int cc_attn_rung(int rung, const void* qkv, void* out,
+                            int64_t n_frames, int seq, int heads, int hidden,
+                            float scale, uint64_t stream) {
+  if (rung < CC_ATTN_SMALL || rung > CC_ATTN_FLASH)
+    return cc::set_error(CC_ERR_INVALID, "cc_attn_rung: no rung %d", rung);
+  return attn_launch(-1, rung, qkv, out, n_frames, seq, heads, hidden, scale,
+                     stream);
+}

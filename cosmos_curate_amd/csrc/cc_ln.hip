@@ -9,7 +9,10 @@
 // reduction trees (sum, sumsq), bf16x4 (8 B) loads/stores (guide §5
 // rule 2: scalar/narrow bf16 access leaves >2x bandwidth on the table;
 // measured 4.7 TB/s at bf16x2).
-// H must be a multiple of 256 (768/1024/3072/4096 all comply).
+// H is one of the instantiated multiples of 256 (768/1024/3072/4096 all
+// comply), 128, or 1152 (SigLIP-so400m): 1152 = 4.5 x 256, so the last of
+// its five 256-column steps covers 128 columns and runs on lanes 0..31 —
+// the idle half loads and stores nothing and adds zeros to the sums.
 //
 // Also here: the row statistics of the folded LayerNorm.
 // cc_ln_stats_bf16 reads x once and writes f32 partial sums (sum, sum of
@@ -45,7 +48,17 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-template <int CHUNK>  // elements per lane (H / 64), multiple of 4
+// Whether lane `lane` holds columns in the 256-column step that starts at
+// 64-column block c of a row of CHUNK blocks.  Constant true wherever the
+// step is whole (always, when CHUNK % 4 == 0).
+template <int CHUNK>
+__device__ __forceinline__ bool step_live(int c, int lane) {
+  return c + 4 <= CHUNK || 4 * lane < (CHUNK - c) * 64;
+}
+
+// CHUNK = H / 64, the 64-column blocks of a row; a lane holds 4 elements
+// of each 256-column step (CHUNK % 4 != 0: see step_live)
+template <int CHUNK>
 __global__ void k_layernorm_bf16(const __bf16* __restrict__ x,
                                  const float* __restrict__ w,
                                  const float* __restrict__ b,
@@ -58,12 +71,13 @@ __global__ void k_layernorm_bf16(const __bf16* __restrict__ x,
   const __bf16* xr = x + row * H;
   __bf16* yr = y + row * H;
 
-  float vals[CHUNK];
+  float vals[(CHUNK + 3) / 4 * 4];
   float s = 0.0f, ss = 0.0f;
 #pragma unroll
   for (int c = 0; c < CHUNK; c += 4) {
     // coalesced: lane i reads elements (c*64 + 4i .. +3)
-    bf16x4 p = *(const bf16x4*)(xr + c * 64 + 4 * lane);
+    bf16x4 p = {};
+    if (step_live<CHUNK>(c, lane)) p = *(const bf16x4*)(xr + c * 64 + 4 * lane);
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       vals[c + j] = (float)p[j];
@@ -79,6 +93,7 @@ __global__ void k_layernorm_bf16(const __bf16* __restrict__ x,
   const float rstd = rsqrtf(var + eps);
 #pragma unroll
   for (int c = 0; c < CHUNK; c += 4) {
+    if (!step_live<CHUNK>(c, lane)) continue;
     const int i0 = c * 64 + 4 * lane;
     f32x4 wv = *(const f32x4*)(w + i0);
     f32x4 bv = *(const f32x4*)(b + i0);
@@ -183,7 +198,9 @@ __device__ __forceinline__ float group_sum(float v) {
 
 // stats[row][blk] = (sum, sum of squares) of x[row][64*blk .. 64*blk+63];
 // one wave per row, read-only on x.  Lane i of step c holds columns
-// c*64 + 4i .. +3, so 16 adjacent lanes hold one 64-column block.
+// c*64 + 4i .. +3, so 16 adjacent lanes hold one 64-column block; in a
+// partial last step (step_live) the idle lanes take part in the shuffles
+// with zeros and write nothing.
 template <int CHUNK>
 __global__ void k_ln_stats_bf16(const __bf16* __restrict__ x,
                                 float2* __restrict__ stats, long M, int H) {
@@ -195,7 +212,9 @@ __global__ void k_ln_stats_bf16(const __bf16* __restrict__ x,
   float2* sr = stats + row * CHUNK;
 #pragma unroll
   for (int c = 0; c < CHUNK; c += 4) {
-    bf16x4 p = *(const bf16x4*)(xr + c * 64 + 4 * lane);
+    const bool live = step_live<CHUNK>(c, lane);
+    bf16x4 p = {};
+    if (live) p = *(const bf16x4*)(xr + c * 64 + 4 * lane);
     float s = 0.0f, ss = 0.0f;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -205,7 +224,7 @@ __global__ void k_ln_stats_bf16(const __bf16* __restrict__ x,
     }
     s = group_sum<16>(s);
     ss = group_sum<16>(ss);
-    if ((lane & 15) == 0) sr[c + (lane >> 4)] = make_float2(s, ss);
+    if (live && (lane & 15) == 0) sr[c + (lane >> 4)] = make_float2(s, ss);
   }
 }
 
@@ -249,16 +268,18 @@ __global__ void k_ln_finalize(const float2* __restrict__ stats,
   }
 }
 
-// the CHUNK (= H / 64) values the two templates are instantiated for; the
+// the CHUNK (= H / 64) values the templates are instantiated for; the
 // entry points reject every other H before they launch, so the switches
-// below need no default
-#define CC_LN_CHUNKS(X) X(4) X(8) X(12) X(16) X(32) X(48) X(64)
+// below need no default.  CC_LN_CHUNKS256: whole 256-column steps, all
+// three templates; CC_LN_CHUNKS adds 18 (H = 1152) for k_layernorm_bf16
+// and k_ln_stats_bf16, which handle the partial last step.
+#define CC_LN_CHUNKS256(X) X(4) X(8) X(12) X(16) X(32) X(48) X(64)
+#define CC_LN_CHUNKS(X) CC_LN_CHUNKS256(X) X(18)
 
-bool has_chunk(int64_t H) {
 #define OR_EQ(C) || H == 64 * C
-  return false CC_LN_CHUNKS(OR_EQ);
+bool has_chunk(int64_t H) { return false CC_LN_CHUNKS(OR_EQ); }
+bool has_chunk256(int64_t H) { return false CC_LN_CHUNKS256(OR_EQ); }
 #undef OR_EQ
-}
 
 }  // namespace
 
@@ -310,12 +331,11 @@ extern "C" int cc_layernorm_bf16(const void* x, const void* w, const void* b,
                                  uint64_t stream) {
   if (!x || !w || !b || !y || M <= 0 || H <= 0)
     return cc::set_error(CC_ERR_INVALID, "bad layernorm args");
-  if ((H % 256 != 0 && H != 128) || H > 64 * 64)
+  if (!cc::ln_h_supported(H))
     return cc::set_error(CC_ERR_UNSUPPORTED,
-                         "H must be 128 or k*256, <=4096 (got %lld)",
+                         "H must be 128, 1152 or an instantiated k*256, "
+                         "<=4096 (got %lld)",
                          (long long)H);
-  if (H != 128 && !has_chunk(H))
-    return cc::set_error(CC_ERR_UNSUPPORTED, "unsupported H %lld", (long long)H);
   dim3 block(256), grid((M + 3) / 4);
   return cc::timed_launch("layernorm_bf16", stream, [&] {
     switch (H / 64) {
@@ -349,7 +369,7 @@ extern "C" int cc_embed_assemble_ln(const void* tok, const void* cls,
   if (H % 256 != 0 || H > 64 * 64)
     return cc::set_error(CC_ERR_UNSUPPORTED, "H must be k*256, <=4096 (got %lld)",
                          (long long)H);
-  if (!has_chunk(H))
+  if (!has_chunk256(H))
     return cc::set_error(CC_ERR_UNSUPPORTED, "unsupported H %lld", (long long)H);
   const long nrows = (long)n_frames * tokens;
   dim3 block(256), grid((nrows + 3) / 4);
@@ -363,7 +383,7 @@ extern "C" int cc_embed_assemble_ln(const void* tok, const void* cls,
                        (const float*)w, (const float*)b, (__bf16*)y,       \
                        nrows, (int)tokens, (int)H, eps);                   \
     break;
-      CC_LN_CHUNKS(CASE)
+      CC_LN_CHUNKS256(CASE)
 #undef CASE
     }
   });

@@ -10,6 +10,7 @@ rocDecode seam).
 from __future__ import annotations
 
 import ctypes
+import functools
 import pathlib
 
 import numpy as np
@@ -139,6 +140,7 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.cc_attn_small.argtypes = lib.cc_attn.argtypes
     lib.cc_attn_mid.argtypes = lib.cc_attn.argtypes
     lib.cc_attn_flash.argtypes = lib.cc_attn.argtypes
+    lib.cc_attn_rung.argtypes = [c.c_int, *lib.cc_attn.argtypes]
     lib.cc_layernorm_bf16.argtypes = [
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
         c.c_float, c.c_uint64]
@@ -265,6 +267,15 @@ def attn_plan(n_frames: int, seq: int, heads: int, hidden: int) -> AttnPlan:
     plan = AttnPlan()
     check(load().cc_attn_plan(n_frames, seq, heads, hidden, ctypes.byref(plan)))
     return plan
+
+
+@functools.lru_cache(maxsize=None)
+def attn_supported(heads: int, hidden: int) -> bool:
+    """Whether cc_attn takes this head geometry — the library's own answer
+    (cc_attn_plan accepts it), so the set of head dims is stated once, in
+    csrc/cc_attn_plan.hpp.  Asked once per geometry."""
+    plan = AttnPlan()
+    return load().cc_attn_plan(1, 1, heads, hidden, ctypes.byref(plan)) == 0
 
 
 class VideoInfo(ctypes.Structure):

@@ -27,6 +27,13 @@ from cosmos_curate_amd.models.clip_vit import ClipVisionTowerAMD
 from cosmos_curate_amd.models.clip_weights import make_clip_vit_b32_weights
 
 _CLIP_MODEL_ID = "openai/clip-vit-base-patch32"
+# hub ids by variant (clip_weights.CONFIGS keys)
+_MODEL_IDS = {
+    "vit_b32": _CLIP_MODEL_ID,
+    "vit_l14": "openai/clip-vit-large-patch14",  # reference clip.py:33
+    "siglip_l16_256": "google/siglip-large-patch16-256",
+    "siglip_so400m_14_224": "google/siglip-so400m-patch14-224",  # BASELINE config #3
+}
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
@@ -161,8 +168,10 @@ class _CLIPImageEmbeddings(torch.nn.Module):
 class CLIPImageEmbeddings(ModelInterface):
     """ModelInterface wrapper (reference clip.py:77-118).
 
-    variant "vit_b32" (flagship) | "vit_l14" (the reference's own CLIP
-    model id, openai/clip-vit-large-patch14 — BASELINE config #3 class).
+    variant: a key of clip_weights.CONFIGS — "vit_b32" (flagship),
+    "vit_l14" (the reference's own CLIP model id,
+    openai/clip-vit-large-patch14), "siglip_l16_256" or
+    "siglip_so400m_14_224" (BASELINE config #3's SigLIP embedder).
     """
 
     def __init__(self, variant: str = "vit_b32",
@@ -178,11 +187,7 @@ class CLIPImageEmbeddings(ModelInterface):
 
     @property
     def model_id_names(self) -> list[str]:
-        if self._variant == "vit_l14":
-            return ["openai/clip-vit-large-patch14"]  # reference clip.py:33
-        if self._variant.startswith("siglip"):
-            return ["google/siglip-large-patch16-256"]  # BASELINE config #3
-        return [_CLIP_MODEL_ID]
+        return [_MODEL_IDS[self._variant]]
 
     def setup(self) -> None:
         self._model = _CLIPImageEmbeddings(self._variant,

@@ -53,15 +53,25 @@ VIT_L14 = VitConfig("vit_l14", hidden=1024, layers=24, heads=16,
                     intermediate=4096, patch=14, proj=768)
 
 # SigLIP-large geometry (google/siglip-large-patch16-256 class): no CLS
-# token, tanh-gelu MLPs, attention-pooling MAP head — the SigLIP-L-class
-# embedder BASELINE config #3 names.  proj == hidden (the MAP head's
+# token, tanh-gelu MLPs, attention-pooling MAP head — a SigLIP-L-class
+# stand-in for the embedder BASELINE config #3 names (see so400m below).  proj == hidden (the MAP head's
 # pooled vector is the embedding; no visual_projection).
 SIGLIP_L16_256 = VitConfig("siglip_l16_256", hidden=1024, layers=24, heads=16,
                            intermediate=4096, patch=16, proj=1024, image=256,
                            has_cls=False, act="gelu_tanh", ln_eps=1e-6)
 
+# SigLIP shape-optimised 400M (google/siglip-so400m-patch14-224): the
+# only patch-14 SigLIP vision tower there is, i.e. what BASELINE config
+# #3's "SigLIP-L/14" can mean.  Head dim 1152/16 = 72; the MLP width 4304
+# is no multiple of 64 (VitEncoderAMD pads it to 4352); 256 tokens.
+SIGLIP_SO400M_14_224 = VitConfig(
+    "siglip_so400m_14_224", hidden=1152, layers=27, heads=16,
+    intermediate=4304, patch=14, proj=1152, image=224, has_cls=False,
+    act="gelu_tanh", ln_eps=1e-6)
+
 CONFIGS = {"vit_b32": VIT_B32, "vit_l14": VIT_L14,
-           "siglip_l16_256": SIGLIP_L16_256}
+           "siglip_l16_256": SIGLIP_L16_256,
+           "siglip_so400m_14_224": SIGLIP_SO400M_14_224}
 
 
 def make_siglip_weights(cfg: VitConfig = SIGLIP_L16_256) -> dict[str, torch.Tensor]:

@@ -1,5 +1,10 @@
 """SigLIP vision tower on the MFMA GEMM path (BASELINE config #3's
-"SigLIP-L/14"-class embedder; geometry = google/siglip-large-patch16-256).
+"SigLIP-L/14" embedder).  Two geometries, both data in clip_weights:
+google/siglip-so400m-patch14-224 (hidden 1152, 16 heads of 72, MLP 4304,
+27 layers — the only patch-14 SigLIP tower released, so what "L/14" can
+mean) and the SigLIP-L stand-in google/siglip-large-patch16-256.  so400m
+runs the same kernels: cc_attn at head dim 72, the LayerNorm family at
+H = 1152, and an MLP width the shared encoder pads to 4352.
 
 Architecture per transformers SiglipVisionModel (the numerics oracle used
 by tests/test_gpu_vit.py::test_siglip_gpu_vs_oracle_cosine): conv patch

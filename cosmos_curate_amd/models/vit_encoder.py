@@ -13,13 +13,19 @@ key prefix; embeddings and pooling stay in the tower files.
   residual fused into its epilogue;
 - attention is one cc_attn call straight off the QKV GEMM output
   (csrc/cc_attn.hip; the kernel for a sequence length is the library's
-  choice, cc::attn_plan); head dims other than 64 take torch sdpa;
+  choice, cc::attn_plan) for every head dim the library takes — the
+  multiples of 8 from 64 to 128, asked of cc_attn_plan itself; any other
+  head dim takes torch sdpa (``force_sdpa = True`` sends every tower
+  there, for A/B runs);
 - LN1 and LN2 never materialise on the GPU: their affine part is folded
   into the QKV / fc1 weights once at construction (fold_layernorm) and the
   GEMM epilogue finishes the normalisation from per-row statistics that
   the GEMM producing the residual stream wrote (DESIGN.md §14;
   ``fold_ln = False`` restores the LN kernel + plain GEMM chain);
 - the remaining layernorms run the fused HIP kernel (f32 statistics);
+- an MLP width that is no multiple of 64 (SigLIP-so400m's 4304) is
+  zero-padded once at construction to the next one, which the GEMM's
+  K % 64 == 0 needs — exact, see VitEncoderAMD;
 - activations are bf16 end-to-end.
 
 No CPU fallback: _linear() requires the HIP extension + a GPU (the tests
@@ -251,10 +257,22 @@ class VitEncoderAMD(torch.nn.Module):
     ``fold_ln`` (default True): on the GPU, LN1 and LN2 are folded into the
     QKV and fc1 GEMMs (_layer_folded).  False runs the LN kernel and the
     plain GEMMs — for A/B runs and parity tests; it is also what CPU
-    tensors and head dims other than 64 get.
+    tensors and head dims cc_attn does not take get.
+
+    ``force_sdpa`` (default False): True sends attention through torch
+    sdpa and its permute copies even where cc_attn takes the head dim (and
+    with it turns the fold off) — for A/B runs and parity tests.
+
+    MLP width: when ``cfg.intermediate`` is no multiple of 64 the fc1 / fc2
+    buffers are padded to the next one (``self.intermediate``): zero rows
+    on w_fc1, b_fc1 and on the folded wf_fc1, s_fc1, c_fc1, zero columns on
+    w_fc2.  Exact: a padded fc1 output is act(0 + 0) = 0 for both
+    activations — on the folded route rstd*(0 - mean*0) + 0 = 0 — and the
+    padded fc2 columns multiply those zeros.  Checkpoints stay unpadded.
     """
 
     fold_ln = True
+    force_sdpa = False
 
     def __init__(
         self, sd: dict[str, torch.Tensor], cfg: cw.VitConfig, prefix: str
@@ -271,6 +289,11 @@ class VitEncoderAMD(torch.nn.Module):
 
         k0 = 3 * cfg.patch * cfg.patch
         self.patch_k = (k0 + 63) // 64 * 64  # cc_gemm needs K % 64 == 0
+        # fc2's K: the MLP width, zero-padded to a multiple of 64
+        self.intermediate = (cfg.intermediate + 63) // 64 * 64
+        mlp_pad = self.intermediate - cfg.intermediate
+        pad_rows = lambda t: torch.nn.functional.pad(  # noqa: E731
+            t, (0, 0, 0, mlp_pad) if t.dim() == 2 else (0, mlp_pad))
         w_patch = sd[prefix + "embeddings.patch_embedding.weight"].reshape(
             cfg.hidden, k0)
         if self.patch_k != k0:
@@ -288,16 +311,17 @@ class VitEncoderAMD(torch.nn.Module):
             reg(f"ln1_b_{i}", to_f32(sd[q + "layer_norm1.bias"]))
             reg(f"ln2_w_{i}", to_f32(sd[q + "layer_norm2.weight"]))
             reg(f"ln2_b_{i}", to_f32(sd[q + "layer_norm2.bias"]))
-            reg(f"w_fc1_{i}", to_bf(sd[q + "mlp.fc1.weight"]))
-            reg(f"b_fc1_{i}", to_f32(sd[q + "mlp.fc1.bias"]))
-            reg(f"w_fc2_{i}", to_bf(sd[q + "mlp.fc2.weight"]))
+            reg(f"w_fc1_{i}", to_bf(pad_rows(sd[q + "mlp.fc1.weight"])))
+            reg(f"b_fc1_{i}", to_f32(pad_rows(sd[q + "mlp.fc1.bias"])))
+            reg(f"w_fc2_{i}", to_bf(torch.nn.functional.pad(
+                sd[q + "mlp.fc2.weight"], (0, mlp_pad))))
             reg(f"b_fc2_{i}", to_f32(sd[q + "mlp.fc2.bias"]))
             # LN1 / LN2 folded into the GEMM they feed (derived, so kept
             # out of the state dict); row order (q, k, v) as in w_qkv
             for name, w, b, ln in (
                 ("qkv", torch.cat([sd[x + "weight"] for x in qkv], dim=0),
                  getattr(self, f"b_qkv_{i}"), "ln1"),
-                ("fc1", sd[q + "mlp.fc1.weight"],
+                ("fc1", pad_rows(sd[q + "mlp.fc1.weight"]),
                  getattr(self, f"b_fc1_{i}"), "ln2"),
             ):
                 folded = fold_layernorm(
@@ -338,11 +362,19 @@ class VitEncoderAMD(torch.nn.Module):
         assert n is not None and patches.shape == (n * g * g, self.patch_k)
         return patches, n
 
+    def _native_attn(self, t: torch.Tensor) -> bool:
+        """Whether attention on ``t`` runs cc_attn: a GPU tensor, a head dim
+        the library takes, and no ``force_sdpa``."""
+        return (
+            not self.force_sdpa and t.is_cuda
+            and hotpath.attn_supported(self.heads, self.cfg.hidden)
+        )
+
     def _attention(self, qkv_flat: torch.Tensor, n: int, seq: int) -> torch.Tensor:
         """(n*seq, 3*hidden) fused QKV rows -> (n*seq, hidden)."""
         hidden = self.cfg.hidden
         hd = hidden // self.heads
-        if qkv_flat.is_cuda and hd == 64:
+        if self._native_attn(qkv_flat):
             # fused attention straight off the QKV GEMM output
             # (csrc/cc_attn.hip) — no permute copies
             lib = hotpath.require_gpu()
@@ -387,10 +419,7 @@ class VitEncoderAMD(torch.nn.Module):
 
     def _folds(self, h: torch.Tensor) -> bool:
         """Whether ``h`` takes the folded-LayerNorm route."""
-        return (
-            self.fold_ln and h.is_cuda
-            and self.cfg.hidden // self.heads == 64
-        )
+        return self.fold_ln and self._native_attn(h)
 
     def _layer_folded(
         self, h: torch.Tensor, stats: torch.Tensor, i: int, n: int, seq: int

@@ -128,13 +128,19 @@ class ClipEmbeddingStage(CuratorStage):
         batch_size: int = 8,
         verbose: bool = False,
         log_stats: bool = False,
+        variant: str = "vit_b32",
+        checkpoint_path: str | None = None,
     ) -> None:
+        """``variant``: the tower, a key of clip_weights.CONFIGS (the
+        embedding width follows it: 512 / 768 / 1024 / 1152);
+        ``checkpoint_path``: a local checkpoint for it, else the
+        deterministic stand-in weights."""
         self._timer = StageTimer(self)
         self._num_gpus = num_gpus_per_worker
         self._batch_size = batch_size
         self._verbose = verbose
         self._log_stats = log_stats
-        self._model = CLIPImageEmbeddings()
+        self._model = CLIPImageEmbeddings(variant, checkpoint_path=checkpoint_path)
 
     @property
     def resources(self) -> CuratorStageResource:
@@ -160,7 +166,7 @@ class ClipEmbeddingStage(CuratorStage):
             batch = np.concatenate([f for _, f in payloads], axis=0)
         else:
             batch = torch.cat([f for _, f in payloads], dim=0)
-        embeds = self._model(batch)  # (sum(counts), 512) f32, unit-norm
+        embeds = self._model(batch)  # (sum(counts), proj) f32, unit-norm
         pos = 0
         for (clip, _), cnt in zip(payloads, counts):
             e = embeds[pos : pos + cnt].mean(dim=0)

@@ -14,7 +14,7 @@ Stage order (reference _assemble_stages):
     ClipTranscodingStage            (fans out via chunk_tasks)
     ClipFrameExtractionStage        (GPU decode->sample->resize)
     ClipFrameCreationStage
-    ClipEmbeddingStage              (CLIP ViT-B/32, MFMA path)
+    ClipEmbeddingStage              (--embedding-model tower, MFMA path)
     ClipWriterStage
 """
 
@@ -30,6 +30,7 @@ from cosmos_curate_amd.core.interfaces import (
     RunnerInterface,
     run_pipeline,
 )
+from cosmos_curate_amd.models.clip_weights import CONFIGS as EMBEDDING_MODELS
 from cosmos_curate_amd.pipelines.video.clipping.clip_extraction_stages import (
     ClipTranscodingStage,
     FixedStrideExtractorStage,
@@ -215,7 +216,8 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
             target_res=(res, res) if res > 0 else (-1, -1),
             log_stats=True,
         ))
-        stages.append(ClipEmbeddingStage(log_stats=True))
+        stages.append(ClipEmbeddingStage(
+            log_stats=True, variant=args.embedding_model))
     stages.append(ClipWriterStage(args.output_clip_path, log_stats=True))
     return stages
 
@@ -242,6 +244,11 @@ def _setup_parser(parser: argparse.ArgumentParser) -> None:
     parser.add_argument("--no-embeddings", "--no-generate-embeddings",
                         dest="generate_embeddings", action="store_false")
     parser.add_argument("--embedding-algorithm", default="clip")
+    parser.add_argument("--embedding-model", default="vit_b32",
+                        choices=sorted(EMBEDDING_MODELS),
+                        help="vision tower of the embedding stage "
+                        "(clip_weights.CONFIGS); frames are resized on device "
+                        "to the tower's input size where they differ")
     parser.add_argument("--aesthetic-threshold", type=float, default=None)
     parser.add_argument("--clip-extraction-target-res", type=int, default=224,
                         help="square target resolution for extracted frames; "

@@ -289,8 +289,9 @@ int cc_gemm_plan(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldr,
 
 /* ---- fused attention (ViT encoder; replaces torch sdpa + the qkv
  * permute copies).  qkv = the fused-QKV GEMM output [n*seq, 3*hidden]
- * bf16; out [n*seq, hidden] bf16; head dim 64; qkv and out 16-byte
- * aligned.  cc_attn runs the rung of the ladder that cc::attn_plan
+ * bf16; out [n*seq, hidden] bf16; head dim hidden/heads = any multiple of 8
+ * from 64 to 128 (64 CLIP/SigLIP-L, 72 SigLIP-so400m, 80 ViT-H, 88 ViT-g,
+ * 104 bigG, ...); qkv and out 16-byte aligned.  cc_attn runs the rung of the ladder that cc::attn_plan
  * (csrc/cc_attn_plan.hpp) picks for seq — callers need not know the
  * thresholds:
  *   small  everything LDS-resident, one workgroup per (frame, head)
@@ -298,10 +299,11 @@ int cc_gemm_plan(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldr,
  *   mid    Q/K fragments straight from global, V^T + P in LDS, Q in 64-row
  *          tiles (ViT-L/14's 257, SigLIP-L16-256's 256)
  *   flash  K/V streamed in 64-row tiles with online softmax, one workgroup
- *          per (frame, head, q-tile) (SigLIP-384/so400m-class towers)
+ *          per (frame, head, q-tile) (SigLIP-384-class towers; above head
+ *          dim 64 also most lengths from 65 to 288, e.g. so400m-224's 256)
  * CC_ERR_INVALID on null or misaligned pointers, non-positive
  * n_frames/seq/heads or a grid past 2^31-1 workgroups; CC_ERR_UNSUPPORTED
- * when hidden != heads*64 — all before any launch. */
+ * when hidden is not heads times such a head dim — all before any launch. */
 int cc_attn(const void* qkv, void* out, int64_t n_frames, int seq, int heads,
             int hidden, float scale, uint64_t stream);
 
@@ -326,6 +328,12 @@ int cc_attn_mid(const void* qkv, void* out, int64_t n_frames, int seq,
                 int heads, int hidden, float scale, uint64_t stream);
 int cc_attn_flash(const void* qkv, void* out, int64_t n_frames, int seq,
                   int heads, int hidden, float scale, uint64_t stream);
+/* A/B entry (tools/attn_hd_bench.py): run rung `rung` (CC_ATTN_*) wherever
+ * it can cover seq, whatever the plan would pick — small seq <= 64, mid
+ * seq <= 288, flash any.  CC_ERR_INVALID on an unknown rung,
+ * CC_ERR_UNSUPPORTED on a seq the rung cannot cover. */
+int cc_attn_rung(int rung, const void* qkv, void* out, int64_t n_frames,
+                 int seq, int heads, int hidden, float scale, uint64_t stream);
 
 /* CLS-query variant (head dim 64, any seq >= 1): attention for ONE query
  * row per (frame, head) against all seq keys/values — the only row of the
@@ -341,7 +349,8 @@ int cc_attn_cls(const void* q, const void* k, const void* v, int64_t ldkv,
                 float scale, uint64_t stream);
 
 /* ---- fused bf16 LayerNorm (replaces torch layer_norm in the ViT
- * forward; f32 stats/affine, H multiple of 256). */
+ * forward; f32 stats/affine; H = 128, 1152 or one of the instantiated
+ * multiples of 256: 256, 512, 768, 1024, 2048, 3072, 4096). */
 int cc_layernorm_bf16(const void* x, const void* w, const void* b, void* y,
                       int64_t M, int64_t H, float eps, uint64_t stream);
 
