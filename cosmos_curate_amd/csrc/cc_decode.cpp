@@ -359,6 +359,22 @@ int cc_decode_stream_format(const cc_decode* s, cc_stream_format* out) {
   return CC_OK;
 }
 
+int cc_decode_stream_transfer(const cc_decode* s,
+                              int32_t* transfer_characteristics,
+                              int32_t* colour_primaries) {
+  if (!s) return cc::set_error(CC_ERR_INVALID, "bad args");
+  if (!s->have_format)
+    return cc::set_error(CC_ERR_INVALID,
+                         "stream transfer unknown before the first sequence "
+                         "header");
+  if (transfer_characteristics)
+    *transfer_characteristics =
+        s->format.video_signal_description.transfer_characteristics;
+  if (colour_primaries)
+    *colour_primaries = s->format.video_signal_description.color_primaries;
+  return CC_OK;
+}
+
 int cc_decode_recycle(cc_decode* s) {
   if (!s || !s->parser) return cc::set_error(CC_ERR_INVALID, "bad session");
   for (int idx : s->mapped) {

@@ -19,6 +19,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
+#include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "cc_common.hpp"
@@ -89,6 +92,10 @@ struct YuvCoef {
   float yoff, cy, cvr, cvg, cug, cub;
 };
 
+// entries of each table of the cc_hdr_tables_build image (f32 then u8)
+constexpr int kHdrTableEntries = 4096;
+static_assert(kHdrTableEntries * 5 == CC_HDR_TABLE_BYTES, "table image size");
+
 // [matrix 0=BT.601 1=BT.709 2=BT.2020-NCL][0 = limited range, 1..3 = full
 // range at depth 8/10/12].  Limited: yoff 16, CY 255/219, chroma scale
 // sc 255/224; full: yoff 0, CY = sc = 255*2^(d-8)/(2^d-1);
@@ -139,7 +146,58 @@ struct YuvBt601Limited8 {
   static constexpr YuvCoef k = kYuvCoef[0][0];
 };
 
-// P = YuvParams or YuvBt601Limited8: one arithmetic definition for both
+// YuvParams plus what the PQ (SMPTE ST 2084) -> SDR chain reads: the two
+// tables of cc_hdr_tables_build on the device and 1/(peak/white)^2.  The
+// scalar and the fused-resize kernel read the tables through the cache;
+// the 8-pixels-per-lane kernel copies the image to LDS first (DESIGN.md §4b
+// has the A/B).
+struct YuvHdrParams : YuvParams {
+  const float* tin;           // [4096] code/16 -> linear light / white
+  const unsigned char* tout;  // [4096] 4095*c^(1/4) -> 255*c^(1/2.4)
+  float inv_w2;
+};
+
+__device__ __forceinline__ float hdr_eotf(float c8, const float* tin) {
+  float i = fminf(fmaxf(floorf(c8 * 16.0f + 0.5f), 0.0f), 4080.0f);
+  return tin[(int)i];
+}
+
+__device__ __forceinline__ unsigned char hdr_oetf(float c,
+                                                  const unsigned char* tout) {
+  float y = sqrtf(sqrtf(c));  // c in [0, 1], so the index is in [0, 4095]
+  return tout[(int)floorf(y * 4095.0f + 0.5f)];
+}
+
+// What becomes of the three f32 R'G'B' values on the 8-bit scale for PQ
+// content, where the SDR types round them to u8: tone-mapped to SDR first.
+// Every step is f32 in this order (the contract tests/hdr_ref.py restates);
+// the only transcendental steps are the two tables, so the result does not
+// depend on a device pow:
+//   L  = tin[clamp(floor(c8*16 + 0.5), 0, 4080)]      inverse PQ / white
+//   BT.2020 -> BT.709 (BT.2087), row = (m0*R + m1*G) + m2*B, max(., 0)
+//   m  = max(max(r, g), b); s = (1 + m*inv_w2) / (1 + m)   extended Reinhard
+//   c  = min(c*s, 1)
+//   out = tout[floor(sqrt(sqrt(c))*4095 + 0.5)]        inverse BT.1886
+// The division and the square roots must be correctly rounded.
+__device__ __forceinline__ uchar3 hdr_finish(float r8, float g8, float b8,
+                                             const YuvHdrParams& p) {
+  const float lr = hdr_eotf(r8, p.tin);
+  const float lg = hdr_eotf(g8, p.tin);
+  const float lb = hdr_eotf(b8, p.tin);
+  const float r = fmaxf((1.6605f * lr + -0.5876f * lg) + -0.0728f * lb, 0.0f);
+  const float g = fmaxf((-0.1246f * lr + 1.1329f * lg) + -0.0083f * lb, 0.0f);
+  const float b = fmaxf((-0.0182f * lr + -0.1006f * lg) + 1.1187f * lb, 0.0f);
+  const float m = fmaxf(fmaxf(r, g), b);
+  const float s = (1.0f + m * p.inv_w2) / (1.0f + m);
+  return {hdr_oetf(fminf(r * s, 1.0f), p.tout),
+          hdr_oetf(fminf(g * s, 1.0f), p.tout),
+          hdr_oetf(fminf(b * s, 1.0f), p.tout)};
+}
+
+// P = YuvParams, YuvBt601Limited8 or YuvHdrParams: one matrix definition
+// for all three.  The finish step is round_u8 per channel, written inside
+// the braces as it always was (handing the three sums to a function first
+// reorders the SDR kernels' instructions), or hdr_finish.
 template <typename P>
 __device__ __forceinline__ uchar3 yuv_to_rgb_u8(unsigned sy, unsigned su,
                                                 unsigned sv, const P& p) {
@@ -147,9 +205,13 @@ __device__ __forceinline__ uchar3 yuv_to_rgb_u8(unsigned sy, unsigned su,
   float u = (float)(su >> p.shift) * p.scale - 128.0f;
   float v = (float)(sv >> p.shift) * p.scale - 128.0f;
   float fy = p.k.cy * yf;
-  return {round_u8(fy + p.k.cvr * v),
-          round_u8(fy + p.k.cvg * v + p.k.cug * u),
-          round_u8(fy + p.k.cub * u)};
+  if constexpr (std::is_same_v<P, YuvHdrParams>)
+    return hdr_finish(fy + p.k.cvr * v, fy + p.k.cvg * v + p.k.cug * u,
+                      fy + p.k.cub * u, p);
+  else
+    return {round_u8(fy + p.k.cvr * v),
+            round_u8(fy + p.k.cvg * v + p.k.cug * u),
+            round_u8(fy + p.k.cub * u)};
 }
 
 // one pixel (full-res coords); T = sample type, pitch in bytes
@@ -168,11 +230,11 @@ __device__ __forceinline__ uchar3 yuv420sp_px(
 // Scalar path: one thread per pixel over columns [x_start, w) of every
 // row — the w % 8 row tails, or whole frames (x_start = 0) whose planes
 // are not 16-byte aligned.
-template <typename T>
+template <typename T, typename P>
 __global__ void k_yuv420sp_to_rgb_px(const unsigned char* __restrict__ y,
                                      const unsigned char* __restrict__ uv,
                                      int n, int h, int w, int x_start,
-                                     size_t pitch, YuvParams p,
+                                     size_t pitch, P p,
                                      unsigned char* __restrict__ out) {
   long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int cw = w - x_start;
@@ -201,16 +263,28 @@ struct __attribute__((packed)) rgb8_run {
 // launcher), 24 contiguous output bytes stored as dwords.  Bandwidth-
 // bound: 3 B/px in at 16 bit, 3 B/px out.  Sample and byte positions are
 // compile-time constants after unrolling, so nothing is indexed at run
-// time and nothing spills.
-template <typename T>
+// time and nothing spills.  With YuvHdrParams each workgroup first copies
+// the table image (20 KB, 16-byte aligned, tin then tout) to LDS: its 2048
+// pixels make 12288 table reads, and with unrelated neighbours those cost
+// a fifth of the kernel's time through the cache and nothing from LDS
+// (DESIGN.md §4b).  8 workgroups of 20 KB fit a CU, so occupancy stays 8.
+template <typename T, typename P>
 __global__ void k_yuv420sp_to_rgb_v8(const unsigned char* __restrict__ y,
                                      const unsigned char* __restrict__ uv,
-                                     int n, int h, int w, size_t pitch,
-                                     YuvParams p,
+                                     int n, int h, int w, size_t pitch, P p,
                                      unsigned char* __restrict__ out) {
   constexpr int BITS = 8 * (int)sizeof(T);
   constexpr int PER = 32 / BITS;  // samples per dword
   constexpr unsigned MASK = (1u << BITS) - 1u;
+  if constexpr (std::is_same_v<P, YuvHdrParams>) {
+    __shared__ uint4 tables[CC_HDR_TABLE_BYTES / 16];
+    const uint4* image = (const uint4*)p.tin;
+    for (int i = threadIdx.x; i < CC_HDR_TABLE_BYTES / 16; i += blockDim.x)
+      tables[i] = image[i];
+    __syncthreads();  // before the early return below: every thread arrives
+    p.tin = (const float*)tables;
+    p.tout = (const unsigned char*)(tables + kHdrTableEntries / 4);
+  }
   long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int runs = w / 8;
   long total = (long)n * h * runs;
@@ -623,10 +697,10 @@ int yuv420sp_check(const void* y, const void* uv, const void* out, int n,
 
 // The launches of one checked call for sample type T: the fused kernel
 // when `resize`, else the vector body and/or the scalar kernel.
-template <typename T>
+template <typename T, typename P>
 int yuv420sp_run(const char* name, const unsigned char* y,
                  const unsigned char* uv, int n, int h, int w, size_t pitch,
-                 const YuvParams& p, bool bt601_limited, unsigned char* out,
+                 const P& p, bool bt601_limited, unsigned char* out,
                  bool resize, int out_h, int out_w, uint64_t stream) {
   const hipStream_t s = (hipStream_t)stream;
   const dim3 block(256);
@@ -636,7 +710,7 @@ int yuv420sp_run(const char* name, const unsigned char* y,
   if (resize)
     return cc::timed_launch(name, stream, [&] {
       const dim3 grid = blocks((long)n * out_h * out_w);
-      if constexpr (sizeof(T) == 1) {
+      if constexpr (sizeof(T) == 1 && std::is_same_v<P, YuvParams>) {
         if (bt601_limited) {
           hipLaunchKernelGGL((k_yuv420sp_to_rgb_resize<T, YuvBt601Limited8>),
                              grid, block, 0, s, y, uv, n, h, w, pitch,
@@ -644,9 +718,8 @@ int yuv420sp_run(const char* name, const unsigned char* y,
           return;
         }
       }
-      hipLaunchKernelGGL((k_yuv420sp_to_rgb_resize<T, YuvParams>), grid,
-                         block, 0, s, y, uv, n, h, w, pitch, p, out, out_h,
-                         out_w);
+      hipLaunchKernelGGL((k_yuv420sp_to_rgb_resize<T, P>), grid, block, 0,
+                         s, y, uv, n, h, w, pitch, p, out, out_h, out_w);
     });
   // 16-byte-aligned planes and pitch: 8-pixel runs go through the vector
   // kernel and only the w % 8 row tails through the scalar one
@@ -654,7 +727,7 @@ int yuv420sp_run(const char* name, const unsigned char* y,
   const int x_vec = aligned ? (w / 8) * 8 : 0;
   if (x_vec > 0) {
     int rc = cc::timed_launch(name, stream, [&] {
-      hipLaunchKernelGGL(k_yuv420sp_to_rgb_v8<T>,
+      hipLaunchKernelGGL((k_yuv420sp_to_rgb_v8<T, P>),
                          blocks((long)n * h * (w / 8)), block, 0, s, y, uv, n,
                          h, w, pitch, p, out);
     });
@@ -662,20 +735,28 @@ int yuv420sp_run(const char* name, const unsigned char* y,
   }
   if (x_vec < w)
     return cc::timed_launch(name, stream, [&] {
-      hipLaunchKernelGGL(k_yuv420sp_to_rgb_px<T>,
+      hipLaunchKernelGGL((k_yuv420sp_to_rgb_px<T, P>),
                          blocks((long)n * h * (w - x_vec)), block, 0, s, y, uv,
                          n, h, w, x_vec, pitch, p, out);
     });
   return CC_OK;
 }
 
-// The one launcher behind cc_yuv420sp_to_rgb* and cc_nv12_to_rgb* (which
-// pass (8, 0, 0)): checks, the conversion parameters, and the choice of
-// instantiation.  `name` is the caller's timing name.
+// the tone-mapping arguments of the cc_yuv420sp_hdr_* entries
+struct HdrArgs {
+  const void* tables;  // device copy of the cc_hdr_tables_build image
+  float inv_w2;
+};
+
+// The one launcher behind cc_yuv420sp_to_rgb*, cc_nv12_to_rgb* (which pass
+// (8, 0, 0)) and cc_yuv420sp_hdr_to_rgb* (which pass `hdr`): checks, the
+// conversion parameters, and the choice of instantiation.  `name` is the
+// caller's timing name.
 int yuv420sp_launch(const char* name, const void* y, const void* uv, int n,
                     int h, int w, size_t pitch, int bit_depth, int matrix,
                     int full_range, void* out, bool resize, int out_h,
-                    int out_w, uint64_t stream) {
+                    int out_w, uint64_t stream,
+                    const HdrArgs* hdr = nullptr) {
   int rc = yuv420sp_check(y, uv, out, n, h, w, pitch, bit_depth, matrix,
                           full_range);
   if (rc != CC_OK) return rc;
@@ -683,13 +764,31 @@ int yuv420sp_launch(const char* name, const void* y, const void* uv, int n,
     return cc::set_error(CC_ERR_INVALID,
                          "yuv420sp: non-positive output size %dx%d", out_w,
                          out_h);
+  if (hdr && (!hdr->tables || ((size_t)hdr->tables & 15)))
+    return cc::set_error(CC_ERR_INVALID, "yuv420sp_hdr: tables must be a "
+                         "non-null, 16-byte-aligned device pointer");
+  if (hdr && !(hdr->inv_w2 >= 0.0f && hdr->inv_w2 <= FLT_MAX))
+    return cc::set_error(CC_ERR_INVALID, "yuv420sp_hdr: inv_w2 must be finite "
+                         "and non-negative (got %g)", (double)hdr->inv_w2);
   const YuvParams p{bit_depth == 8 ? 0 : 16 - bit_depth,
                     1.0f / (float)(1 << (bit_depth - 8)),
                     kYuvCoef[matrix][full_range ? 1 + (bit_depth - 8) / 2 : 0]};
-  auto run = bit_depth == 8 ? yuv420sp_run<uint8_t> : yuv420sp_run<uint16_t>;
-  return run(name, (const unsigned char*)y, (const unsigned char*)uv, n, h, w,
-             pitch, p, matrix == 0 && !full_range, (unsigned char*)out, resize,
-             out_h, out_w, stream);
+  const unsigned char* yb = (const unsigned char*)y;
+  const unsigned char* uvb = (const unsigned char*)uv;
+  if (hdr) {
+    const YuvHdrParams hp{
+        p, (const float*)hdr->tables,
+        (const unsigned char*)hdr->tables + kHdrTableEntries * sizeof(float),
+        hdr->inv_w2};
+    auto run = bit_depth == 8 ? yuv420sp_run<uint8_t, YuvHdrParams>
+                              : yuv420sp_run<uint16_t, YuvHdrParams>;
+    return run(name, yb, uvb, n, h, w, pitch, hp, false, (unsigned char*)out,
+               resize, out_h, out_w, stream);
+  }
+  auto run = bit_depth == 8 ? yuv420sp_run<uint8_t, YuvParams>
+                            : yuv420sp_run<uint16_t, YuvParams>;
+  return run(name, yb, uvb, n, h, w, pitch, p, matrix == 0 && !full_range,
+             (unsigned char*)out, resize, out_h, out_w, stream);
 }
 
 }  // namespace
@@ -782,6 +881,58 @@ int cc_yuv420sp_to_rgb_resize(const void* y, const void* uv, int n, int src_h,
   return yuv420sp_launch("yuv420sp_to_rgb_resize", y, uv, n, src_h, src_w,
                          pitch_bytes, bit_depth, matrix, full_range, out_rgb,
                          true, out_h, out_w, stream);
+}
+
+int cc_hdr_tables_build(int transfer, float reference_white_nits,
+                        void* host_out) {
+  if (!host_out) return cc::set_error(CC_ERR_INVALID, "hdr tables: null out");
+  if (transfer != CC_HDR_TRANSFER_PQ)
+    return cc::set_error(CC_ERR_UNSUPPORTED, "hdr tables: transfer %d is not "
+                         "built (1 = PQ is)", transfer);
+  if (!(reference_white_nits > 0.0f && reference_white_nits <= FLT_MAX))
+    return cc::set_error(CC_ERR_INVALID, "hdr tables: reference white must be "
+                         "positive and finite (got %g)",
+                         (double)reference_white_nits);
+  // SMPTE ST 2084 EOTF, in double; each entry rounded once
+  const double m1 = 2610.0 / 16384.0, m2 = 2523.0 / 4096.0 * 128.0;
+  const double c1 = 3424.0 / 4096.0, c2 = 2413.0 / 4096.0 * 32.0,
+               c3 = 2392.0 / 4096.0 * 32.0;
+  float* tin = (float*)host_out;
+  for (int i = 0; i < kHdrTableEntries; i++) {
+    double nits = 0.0;
+    if (i <= 4080) {
+      const double e = pow(i / 4080.0, 1.0 / m2);
+      nits = 10000.0 * pow(fmax(e - c1, 0.0) / (c2 - c3 * e), 1.0 / m1);
+    }
+    tin[i] = (float)(nits / (double)reference_white_nits);
+  }
+  unsigned char* tout = (unsigned char*)(tin + kHdrTableEntries);
+  for (int j = 0; j < kHdrTableEntries; j++)
+    tout[j] =
+        (unsigned char)floor(255.0 * pow(j / 4095.0, 4.0 / 2.4) + 0.5);
+  return CC_OK;
+}
+
+int cc_yuv420sp_hdr_to_rgb(const void* y, const void* uv, int n, int h, int w,
+                           size_t pitch_bytes, int bit_depth, int matrix,
+                           int full_range, const void* tables_dev,
+                           float inv_w2, void* out_rgb, uint64_t stream) {
+  const HdrArgs hdr{tables_dev, inv_w2};
+  return yuv420sp_launch("yuv420sp_hdr_to_rgb", y, uv, n, h, w, pitch_bytes,
+                         bit_depth, matrix, full_range, out_rgb, false, 0, 0,
+                         stream, &hdr);
+}
+
+int cc_yuv420sp_hdr_to_rgb_resize(const void* y, const void* uv, int n,
+                                  int src_h, int src_w, size_t pitch_bytes,
+                                  int bit_depth, int matrix, int full_range,
+                                  const void* tables_dev, float inv_w2,
+                                  void* out_rgb, int out_h, int out_w,
+                                  uint64_t stream) {
+  const HdrArgs hdr{tables_dev, inv_w2};
+  return yuv420sp_launch("yuv420sp_hdr_to_rgb_resize", y, uv, n, src_h, src_w,
+                         pitch_bytes, bit_depth, matrix, full_range, out_rgb,
+                         true, out_h, out_w, stream, &hdr);
 }
 
 int cc_resize_bilinear_u8(const void* in, int n, int src_h, int src_w,

@@ -77,6 +77,8 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.cc_decode_map_frames.argtypes = [
         c.c_void_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]
     lib.cc_decode_stream_format.argtypes = [c.c_void_p, c.c_void_p]
+    lib.cc_decode_stream_transfer.argtypes = [
+        c.c_void_p, c.POINTER(c.c_int32), c.POINTER(c.c_int32)]
     lib.cc_decode_recycle.argtypes = [c.c_void_p]
     lib.cc_decode_destroy.argtypes = [c.c_void_p]
 
@@ -98,6 +100,15 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.cc_yuv420sp_to_rgb_resize.argtypes = [
         c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_size_t,
         c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_int, c.c_int, c.c_uint64]
+    lib.cc_hdr_tables_build.argtypes = [c.c_int, c.c_float, c.c_void_p]
+    lib.cc_yuv420sp_hdr_to_rgb.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_size_t,
+        c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_float, c.c_void_p,
+        c.c_uint64]
+    lib.cc_yuv420sp_hdr_to_rgb_resize.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_size_t,
+        c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_float, c.c_void_p,
+        c.c_int, c.c_int, c.c_uint64]
     lib.cc_resize_bilinear_u8.argtypes = [
         c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_int, c.c_int,
         c.c_uint64]
@@ -219,6 +230,78 @@ def yuv_to_rgb_resize(
     check(load().cc_yuv420sp_to_rgb_resize(
         y, uv, n, src_h, src_w, pitch_bytes, bit_depth, matrix,
         int(bool(full_range)), out_rgb, out_h, out_w, stream))
+
+
+HDR_TRANSFER_PQ = 1  # CC_HDR_TRANSFER_PQ
+HDR_TABLE_BYTES = 20480  # CC_HDR_TABLE_BYTES: f32 tin[4096] then u8 tout[4096]
+
+
+def hdr_tables_build(
+    transfer: int = HDR_TRANSFER_PQ, reference_white_nits: float = 203.0,
+) -> npt.NDArray[np.uint8]:
+    """The table image of cc_hdr_tables_build as host bytes (host-only, no
+    GPU needed): ``img[:16384].view(np.float32)`` is ``tin``,
+    ``img[16384:]`` is ``tout``.  Raises on a transfer without tables or a
+    reference white that is not positive and finite."""
+    img = np.empty(HDR_TABLE_BYTES, dtype=np.uint8)
+    check(load().cc_hdr_tables_build(
+        transfer, reference_white_nits, img.ctypes.data_as(ctypes.c_void_p)))
+    return img
+
+
+_hdr_tables_dev: dict[tuple[int, int, float], object] = {}
+
+
+def hdr_tables(
+    transfer: int = HDR_TRANSFER_PQ, reference_white_nits: float = 203.0,
+):
+    """The same image as a uint8 device tensor on the current device, built
+    and uploaded once per (device, transfer, reference white); pass its
+    ``data_ptr()`` as ``tables``."""
+    import torch
+
+    key = (torch.cuda.current_device(), int(transfer), float(reference_white_nits))
+    dev = _hdr_tables_dev.get(key)
+    if dev is None:
+        img = hdr_tables_build(transfer, reference_white_nits)
+        dev = torch.from_numpy(img).to(torch.device("cuda", key[0]))
+        _hdr_tables_dev[key] = dev
+    return dev
+
+
+def hdr_inv_w2(peak_nits: float, reference_white_nits: float = 203.0) -> float:
+    """The tone-mapping constant 1/(peak/white)^2, rounded to f32 once."""
+    if not (peak_nits > 0 and reference_white_nits > 0):
+        raise ValueError("peak and reference white must be positive")
+    ratio = float(peak_nits) / float(reference_white_nits)
+    return float(np.float32(1.0 / (ratio * ratio)))
+
+
+def yuv_hdr_to_rgb(
+    y: int, uv: int, n: int, h: int, w: int, pitch_bytes: int, out_rgb: int,
+    stream: int, *, tables: int, inv_w2: float,
+    bit_depth: int = 10, matrix: int = 2, full_range: bool = False,
+) -> None:
+    """PQ 4:2:0 semi-planar -> tone-mapped SDR RGB at full resolution on
+    device pointers (cc_yuv420sp_hdr_to_rgb).  No fallback: a failing call
+    raises."""
+    check(load().cc_yuv420sp_hdr_to_rgb(
+        y, uv, n, h, w, pitch_bytes, bit_depth, matrix, int(bool(full_range)),
+        tables, inv_w2, out_rgb, stream))
+
+
+def yuv_hdr_to_rgb_resize(
+    y: int, uv: int, n: int, src_h: int, src_w: int, pitch_bytes: int,
+    out_rgb: int, out_h: int, out_w: int, stream: int, *, tables: int,
+    inv_w2: float, bit_depth: int = 10, matrix: int = 2,
+    full_range: bool = False,
+) -> None:
+    """yuv_to_rgb_resize for PQ content: every tap tone-mapped to SDR before
+    the blend (cc_yuv420sp_hdr_to_rgb_resize).  No fallback: a failing call
+    raises."""
+    check(load().cc_yuv420sp_hdr_to_rgb_resize(
+        y, uv, n, src_h, src_w, pitch_bytes, bit_depth, matrix,
+        int(bool(full_range)), tables, inv_w2, out_rgb, out_h, out_w, stream))
 
 
 def estimate_motion(
@@ -353,6 +436,14 @@ class DecodeSession:
         fmt = StreamFormat()
         check(self._lib.cc_decode_stream_format(self._h, ctypes.byref(fmt)))
         return fmt
+
+    def stream_transfer(self) -> tuple[int, int]:
+        """(transfer_characteristics, colour_primaries), the H.273 codes of
+        the stream (16 = PQ, 9 = BT.2020); raises when stream_format does."""
+        tc, cp = ctypes.c_int32(), ctypes.c_int32()
+        check(self._lib.cc_decode_stream_transfer(
+            self._h, ctypes.byref(tc), ctypes.byref(cp)))
+        return tc.value, cp.value
 
     def recycle(self) -> None:
         check(self._lib.cc_decode_recycle(self._h))

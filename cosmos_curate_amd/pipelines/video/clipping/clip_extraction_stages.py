@@ -242,7 +242,8 @@ def _slice_raw_clip(raw: bytes | np.ndarray, span: tuple[float, float]) -> np.nd
     num = int(round(fps))
     depth, matrix, full_range, _ = raw_backend.parse_format(raw)
     hdr = raw_backend.pack_header(last - first, h, w, num, 1, bit_depth=depth,
-                                  matrix=matrix, full_range=full_range)
+                                  matrix=matrix, full_range=full_range,
+                                  transfer=raw_backend.parse_transfer(raw))
     body = buf[raw_backend.HEADER_SIZE + first * fsz:
                raw_backend.HEADER_SIZE + last * fsz]
     return np.concatenate([np.frombuffer(hdr, dtype=np.uint8), body])

@@ -13,7 +13,8 @@ MI355X path:
     NV12 surfaces -> HBM (rocDecode | raw upload)    [device]
     fused YUV->RGB + bilinear resize kernel          [device, §2b rows 3-5]
       (cc_yuv420sp_to_rgb_resize for every depth and colour standard;
-       8-bit BT.601 limited gives the bits of cc_nv12_to_rgb_resize)
+       8-bit BT.601 limited gives the bits of cc_nv12_to_rgb_resize;
+       cc_yuv420sp_hdr_to_rgb_resize for PQ clips under hdr="tonemap")
     duplicate-count broadcast (cc_gather_frames_u8)  [device]
 
 Output frames live on DEVICE as torch uint8 NHWC tensors keyed by
@@ -58,6 +59,11 @@ _FORCED_MATRIX = {"bt601": 0, "bt709": 1, "bt2020": 2}
 # H.273 matrix_coefficients -> kernel matrix code; everything else
 # (unspecified = 2 included) converts as BT.601
 _H273_MATRIX = {1: 1, 5: 0, 6: 0, 9: 2}
+_H273_TRANSFER_PQ = 16  # SMPTE ST 2084
+# colour_primaries under which a PQ stream is tone-mapped: BT.2020, or
+# nothing signalled (0 reserved, 2 unspecified) — BT.2100 content
+_H273_PQ_PRIMARIES = (0, 2, 9)
+_HDR_MODES = ("off", "tonemap")
 
 
 class ClipFrameExtractionStage(CuratorStage):
@@ -68,6 +74,15 @@ class ClipFrameExtractionStage(CuratorStage):
     cvcuda conversion does), ``"bt709"`` / ``"bt2020"`` (that matrix,
     limited range), or ``"stream"`` (matrix and range the clip signals:
     the decoder's sequence header, or the raw payload's header).
+
+    ``hdr`` says what to do with clips that signal the PQ transfer function
+    (HDR10): ``"off"`` (default) converts them like any other clip,
+    ``"tonemap"`` maps them to SDR BT.709 in the same kernel (inverse PQ,
+    BT.2020 -> BT.709, extended Reinhard up to ``hdr_peak_nits`` with
+    diffuse white at ``hdr_reference_white_nits``, display gamma 2.4).
+    Their matrix and range are then the ones the clip signals, whatever
+    ``color_standard`` says, and BT.2020-NCL when it signals none.  Every
+    other clip takes the same call as under ``"off"``.
     """
 
     def __init__(
@@ -83,10 +98,26 @@ class ClipFrameExtractionStage(CuratorStage):
         log_stats: bool = False,
         to_host: bool = False,
         color_standard: str = "bt601",
+        hdr: str = "off",
+        hdr_peak_nits: float = 1000.0,
+        hdr_reference_white_nits: float = 203.0,
     ) -> None:
         if color_standard != "stream" and color_standard not in _FORCED_MATRIX:
             msg = (f"color_standard must be one of bt601, bt709, bt2020, "
                    f"stream; got {color_standard!r}")
+            raise ValueError(msg)
+        if hdr not in _HDR_MODES:
+            msg = f"hdr must be one of off, tonemap; got {hdr!r}"
+            raise ValueError(msg)
+        for name, nits in (("hdr_peak_nits", hdr_peak_nits),
+                           ("hdr_reference_white_nits", hdr_reference_white_nits)):
+            if isinstance(nits, bool) or not isinstance(nits, (int, float)) \
+                    or not math.isfinite(nits) or nits <= 0:
+                msg = f"{name} must be a positive finite number; got {nits!r}"
+                raise ValueError(msg)
+        if hdr_peak_nits < hdr_reference_white_nits:
+            msg = (f"hdr_peak_nits ({hdr_peak_nits}) must not be below "
+                   f"hdr_reference_white_nits ({hdr_reference_white_nits})")
             raise ValueError(msg)
         if target_fps is None:
             target_fps = [2]
@@ -101,6 +132,9 @@ class ClipFrameExtractionStage(CuratorStage):
         self._log_stats = log_stats
         self._to_host = to_host
         self._color_standard = color_standard
+        self._hdr = hdr
+        self._hdr_peak_nits = float(hdr_peak_nits)
+        self._hdr_white_nits = float(hdr_reference_white_nits)
 
     @property
     def resources(self) -> CuratorStageResource:
@@ -121,6 +155,27 @@ class ClipFrameExtractionStage(CuratorStage):
             return matrix, full_range
         return _FORCED_MATRIX[self._color_standard], False
 
+    def _convert_resize(
+        self, y: int, uv: int, n: int, src_h: int, src_w: int, pitch: int,
+        out_rgb: int, out_h: int, out_w: int, stream: int, *,
+        bit_depth: int, matrix: int, full_range: bool, pq: bool,
+    ) -> None:
+        """The one conversion launch of both routes: the tone-mapping entry
+        for a PQ clip under ``hdr="tonemap"`` (``pq``), else the SDR one."""
+        if not pq:
+            hotpath.yuv_to_rgb_resize(
+                y, uv, n, src_h, src_w, pitch, out_rgb, out_h, out_w, stream,
+                bit_depth=bit_depth, matrix=matrix, full_range=full_range,
+            )
+            return
+        tables = hotpath.hdr_tables(hotpath.HDR_TRANSFER_PQ, self._hdr_white_nits)
+        hotpath.yuv_hdr_to_rgb_resize(
+            y, uv, n, src_h, src_w, pitch, out_rgb, out_h, out_w, stream,
+            tables=tables.data_ptr(),
+            inv_w2=hotpath.hdr_inv_w2(self._hdr_peak_nits, self._hdr_white_nits),
+            bit_depth=bit_depth, matrix=matrix, full_range=full_range,
+        )
+
     # ---- device pipeline -------------------------------------------------
     def _extract_clip_frames(
         self, data: bytes, sample_rate_fps: float
@@ -131,7 +186,12 @@ class ClipFrameExtractionStage(CuratorStage):
             ts = raw_backend.timestamps(data)
             n_frames, src_h, src_w, _ = raw_backend.parse_header(data)
             depth, sig_matrix, sig_full, bps = raw_backend.parse_format(data)
-            matrix, full_range = self._color(sig_matrix, sig_full)
+            pq = (self._hdr == "tonemap"
+                  and raw_backend.parse_transfer(data) == raw_backend.TRANSFER_PQ)
+            if pq:  # BT.2100 content: the signalled matrix, never a forced one
+                matrix, full_range = sig_matrix, sig_full
+            else:
+                matrix, full_range = self._color(sig_matrix, sig_full)
         else:
             rc = lib.cc_rocdecode_available()
             if rc != 0:
@@ -153,10 +213,10 @@ class ClipFrameExtractionStage(CuratorStage):
 
         n_sel = len(idx)
         rgb = torch.empty((n_sel, th, tw, 3), dtype=torch.uint8, device=dev)
-        hotpath.yuv_to_rgb_resize(
+        self._convert_resize(
             y_dev.data_ptr(), uv_dev.data_ptr(), n_sel, src_h, src_w,
             src_w * bps, rgb.data_ptr(), th, tw, stream,
-            bit_depth=depth, matrix=matrix, full_range=full_range,
+            bit_depth=depth, matrix=matrix, full_range=full_range, pq=pq,
         )
         total = int(counts.sum())
         if total == n_sel and np.all(counts == 1):
@@ -225,9 +285,20 @@ class ClipFrameExtractionStage(CuratorStage):
                     # (NV12 <-> P016) only between batches, so every frame
                     # of this batch has this format
                     fmt = sess.stream_format()
-                    matrix, full_range = self._color(
-                        _H273_MATRIX.get(int(fmt.matrix_coefficients), 0),
-                        bool(fmt.full_range))
+                    pq = False
+                    if self._hdr == "tonemap":
+                        transfer, primaries = sess.stream_transfer()
+                        pq = (transfer == _H273_TRANSFER_PQ
+                              and primaries in _H273_PQ_PRIMARIES)
+                    if pq:
+                        # the stream's own matrix and range; PQ with none
+                        # signalled is BT.2100: BT.2020-NCL
+                        matrix = _H273_MATRIX.get(int(fmt.matrix_coefficients), 2)
+                        full_range = bool(fmt.full_range)
+                    else:
+                        matrix, full_range = self._color(
+                            _H273_MATRIX.get(int(fmt.matrix_coefficients), 0),
+                            bool(fmt.full_range))
                     launched = False
                     for f in frames:
                         slot = slot_by_tick.get(int(f.pts))
@@ -245,11 +316,11 @@ class ClipFrameExtractionStage(CuratorStage):
                                    f"{tuple(rgb.shape[1:3])} -> {(oh, ow)} "
                                    "with target_res unset")
                             raise RuntimeError(msg)
-                        hotpath.yuv_to_rgb_resize(
+                        self._convert_resize(
                             f.y, f.uv, 1, fh, fw, f.pitch,
                             rgb[slot].data_ptr(), oh, ow, stream,
                             bit_depth=int(fmt.bit_depth), matrix=matrix,
-                            full_range=full_range,
+                            full_range=full_range, pq=pq,
                         )
                         filled[slot] = True
                         launched = True
@@ -368,10 +439,16 @@ def extract_frames(
     sample_rate_fps: float,
     target_res: tuple[int, int] = (-1, -1),
     to_host: bool = False,
+    hdr: str = "off",
+    hdr_peak_nits: float = 1000.0,
+    hdr_reference_white_nits: float = 203.0,
 ) -> "torch.Tensor | np.ndarray":
     """One-off frame extraction (reference decoder_utils.extract_frames
     shape, used by the embedding stage's doubling-fps re-extraction,
     internvideo2_stages.py:157-175)."""
-    stage = ClipFrameExtractionStage(target_res=target_res, to_host=to_host)
+    stage = ClipFrameExtractionStage(
+        target_res=target_res, to_host=to_host, hdr=hdr,
+        hdr_peak_nits=hdr_peak_nits,
+        hdr_reference_white_nits=hdr_reference_white_nits)
     frames = stage._extract_clip_frames(data, float(sample_rate_fps))
     return frames.cpu().numpy() if to_host else frames

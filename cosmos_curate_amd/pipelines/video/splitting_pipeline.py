@@ -170,6 +170,8 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
                 target_fps=sorted(fps_targets),
                 target_res=(res, res) if res > 0 else (-1, -1),
                 log_stats=True,
+                hdr=getattr(args, "hdr", "off"),
+                hdr_peak_nits=getattr(args, "hdr_peak_nits", 1000.0),
             )
         )
     if args.aesthetic_threshold is not None:
@@ -254,6 +256,12 @@ def _setup_parser(parser: argparse.ArgumentParser) -> None:
                         help="square target resolution for extracted frames; "
                         "-1 disables resize (reference flag; the embedder "
                         "resizes on device if needed)")
+    parser.add_argument("--hdr", choices=["off", "tonemap"], default="off",
+                        help="clips that signal the PQ transfer function "
+                        "(HDR10): off converts them like SDR, tonemap maps "
+                        "them to SDR BT.709 in the conversion kernel")
+    parser.add_argument("--hdr-peak-nits", type=float, default=1000.0,
+                        help="luminance that --hdr tonemap maps to white")
     parser.add_argument("--motion-filter", choices=["disable", "enable", "score-only"],
                         default="disable")
     parser.add_argument("--motion-global-mean-threshold", type=float, default=0.00098)
@@ -294,7 +302,10 @@ def split(args: argparse.Namespace, runner: RunnerInterface | None = None) -> di
     if getattr(args, "dry_run", False):
         for st in stages:
             inner = st.stage if hasattr(st, "stage") else st
-            print(type(inner).__name__)
+            hdr = getattr(inner, "_hdr", "off")
+            print(type(inner).__name__ if hdr == "off" else
+                  f"{type(inner).__name__} hdr={hdr} "
+                  f"hdr_peak_nits={inner._hdr_peak_nits:g}")
         return {"dry_run": True, "num_input_videos": len(input_tasks),
                 "num_stages": len(stages)}
     save_cfg = None

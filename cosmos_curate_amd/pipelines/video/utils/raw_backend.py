@@ -23,6 +23,12 @@ streams).  Same magic, same 32-byte header, so routing on the magic and
     samples little-endian and MSB-aligned (value << (16 - bit_depth))
 ``matrix`` is the conversion-kernel code (0 BT.601, 1 BT.709, 2 BT.2020-NCL),
 the colour standard the clip signals.
+
+Version 3 — version 2 whose colour byte also carries the transfer function
+in bits 2..3: ``matrix | transfer << 2 | full_range << 7`` with ``transfer``
+0 = unspecified / SDR, 1 = PQ (SMPTE ST 2084; cc_hdr_tables_build's code).
+Only written for a nonzero transfer, so every version-2 payload keeps its
+bytes.
 """
 
 from __future__ import annotations
@@ -37,28 +43,34 @@ _HDR = struct.Struct("<10sHIIIII")
 _HDR2 = struct.Struct("<10sHIIIIHBB")
 HEADER_SIZE = _HDR.size
 assert _HDR2.size == HEADER_SIZE
+TRANSFER_SDR, TRANSFER_PQ = 0, 1
+TRANSFERS = (TRANSFER_SDR, TRANSFER_PQ)
 
 
 def pack_header(
     n: int, h: int, w: int, fps_num: int, fps_den: int = 1, *,
     bit_depth: int = 8, matrix: int = 0, full_range: bool = False,
+    transfer: int = 0,
 ) -> bytes:
     """The 32-byte payload header alone (for zero-copy body slicing).
 
     The defaults give a version-1 (8-bit NV12) header; ``bit_depth`` 10 or
-    12 gives version 2.  Version 1 has no room for colour signalling, so an
-    8-bit header takes none.
+    12 gives version 2, and version 3 with a nonzero ``transfer``.  Version
+    1 has no room for colour signalling, so an 8-bit header takes none.
     """
+    if transfer not in TRANSFERS:
+        raise ValueError(f"transfer must be 0 (SDR) or 1 (PQ), got {transfer}")
     if bit_depth == 8:
-        if matrix != 0 or full_range:
+        if matrix != 0 or full_range or transfer:
             raise ValueError("version-1 (8-bit) headers carry no colour signalling")
         return _HDR.pack(MAGIC, 1, n, h, w, fps_num, fps_den)
     if bit_depth not in (10, 12):
         raise ValueError(f"bit_depth must be 8, 10 or 12, got {bit_depth}")
     if matrix not in (0, 1, 2):
         raise ValueError(f"matrix must be 0, 1 or 2, got {matrix}")
-    return _HDR2.pack(MAGIC, 2, n, h, w, fps_num, fps_den, bit_depth,
-                      matrix | (int(bool(full_range)) << 7))
+    return _HDR2.pack(MAGIC, 3 if transfer else 2, n, h, w, fps_num, fps_den,
+                      bit_depth,
+                      matrix | (transfer << 2) | (int(bool(full_range)) << 7))
 
 
 def encode_raw_nv12(
@@ -77,14 +89,16 @@ def encode_raw_nv12(
 def encode_raw_p016(
     y: npt.NDArray[np.uint16], uv: npt.NDArray[np.uint16], fps_num: int,
     fps_den: int = 1, *, bit_depth: int, matrix: int = 0, full_range: bool = False,
+    transfer: int = 0,
 ) -> bytes:
     """Pack (N,H,W) Y + (N,H/2,W) interleaved-UV u16 planes (MSB-aligned
-    samples) into a version-2 payload."""
+    samples) into a version-2 payload (version 3 with a nonzero
+    ``transfer``)."""
     n, h, w = y.shape
     assert y.dtype == np.uint16 and uv.dtype == np.uint16, (y.dtype, uv.dtype)
     assert uv.shape == (n, h // 2, w), (y.shape, uv.shape)
     hdr = pack_header(n, h, w, fps_num, fps_den, bit_depth=bit_depth,
-                      matrix=matrix, full_range=full_range)
+                      matrix=matrix, full_range=full_range, transfer=transfer)
     frames = np.concatenate(
         [np.concatenate([y[i].reshape(-1), uv[i].reshape(-1)]) for i in range(n)]
     )
@@ -101,12 +115,25 @@ def _unpack(data: bytes) -> tuple[int, int, int, int, int, int, int, bool]:
     """(n, h, w, fps_num, fps_den, bit_depth, matrix, full_range)."""
     head = bytes(data[:HEADER_SIZE])
     magic, ver, n, h, w, num, den = _HDR.unpack_from(head)
-    assert magic == MAGIC and ver in (1, 2), (magic, ver)
+    assert magic == MAGIC and ver in (1, 2, 3), (magic, ver)
     if ver == 1:
         return n, h, w, num, den, 8, 0, False
     _, _, n, h, w, num, den, depth, flags = _HDR2.unpack_from(head)
+    if ver == 3:
+        # bits 2..3 are the transfer (parse_transfer); the rest as version 2
+        assert (flags >> 2) & 3 in TRANSFERS and not flags & 0x70, flags
+        flags &= ~0x0C
     assert depth in (10, 12) and (flags & 0x7F) in (0, 1, 2), (depth, flags)
     return n, h, w, num, den, depth, flags & 0x7F, bool(flags >> 7)
+
+
+def parse_transfer(data: bytes) -> int:
+    """The transfer function the payload signals: 0 unspecified / SDR (every
+    version-1 and version-2 payload), 1 PQ."""
+    _unpack(data)  # the header checks
+    head = bytes(data[:HEADER_SIZE])
+    ver = _HDR.unpack_from(head)[1]
+    return (_HDR2.unpack_from(head)[8] >> 2) & 3 if ver == 3 else TRANSFER_SDR
 
 
 def parse_header(data: bytes) -> tuple[int, int, int, float]:
@@ -172,11 +199,13 @@ def make_synthetic_clip(
 def make_synthetic_clip_p016(
     n_frames: int, height: int, width: int, fps: int, seed: int, *,
     bit_depth: int = 10, matrix: int = 0, full_range: bool = False,
+    transfer: int = 0,
 ) -> bytes:
     """Seeded moving-gradient + noise P016 clip with TRUE ``bit_depth``-bit
     content: the gradient and the noise live on the full 2^bit_depth code
     range (the low bits below 8-bit precision are populated), then samples
-    are MSB-aligned as a decoder surface would hold them."""
+    are MSB-aligned as a decoder surface would hold them.  ``transfer`` only
+    labels the payload (version 3 when nonzero); the samples are the same."""
     rng = np.random.default_rng(seed)
     top = 1 << bit_depth
     step = top // 256
@@ -190,4 +219,5 @@ def make_synthetic_clip_p016(
     return encode_raw_p016(
         (y << shift).astype(np.uint16), (uv << shift).astype(np.uint16), fps,
         bit_depth=bit_depth, matrix=matrix, full_range=full_range,
+        transfer=transfer,
     )

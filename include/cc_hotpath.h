@@ -124,6 +124,14 @@ typedef struct cc_stream_format {
       bytes_per_sample;
 } cc_stream_format;
 int  cc_decode_stream_format(const cc_decode_t* s, cc_stream_format* out);
+/* The rest of the sequence header's video_signal_description, kept out of
+ * cc_stream_format so that struct keeps its layout: the H.273
+ * transfer_characteristics (16 = SMPTE ST 2084 PQ, 18 = HLG, 1 = BT.709,
+ * 2 unspecified) and colour_primaries (9 = BT.2020) codes.  Either pointer
+ * may be NULL.  Valid when cc_decode_stream_format is. */
+int  cc_decode_stream_transfer(const cc_decode_t* s,
+                               int32_t* transfer_characteristics,
+                               int32_t* colour_primaries);
 /* Return every surface handed out by map_frames to the decoder pool
  * (rocDecParserMarkFrameForReuse).  Call after the consuming kernels
  * complete. */
@@ -181,6 +189,56 @@ int cc_yuv420sp_to_rgb_resize(const void* y, const void* uv, int n,
                               int bit_depth, int matrix, int full_range,
                               void* out_rgb, int out_h, int out_w,
                               uint64_t stream);
+/* ---- PQ (HDR10) -> SDR tone mapping in the same conversion ------------
+ * No counterpart in the reference (cvcuda's conversion is fixed), opt-in
+ * like the matrix choice above.  For streams whose transfer function is
+ * SMPTE ST 2084 (H.273 transfer_characteristics 16) the R'G'B' values are
+ * PQ code values, not gamma-encoded ones; these entries put the chain below
+ * between the matrix and the u8 result.  With r8, g8, b8 the three f32
+ * values cc_yuv420sp_to_rgb rounds to u8 (8-bit scale at any depth), every
+ * step f32 and in this order, bit-exact vs tests/hdr_ref.py:
+ *   L   = tin[clamp(floor(c8*16 + 0.5), 0, 4080)]   per channel: inverse PQ
+ *         over reference white, on the 12-bit grid of the 8-bit scale
+ *   BT.2020 -> BT.709 linear (BT.2087): rows (1.6605, -0.5876, -0.0728),
+ *         (-0.1246, 1.1329, -0.0083), (-0.0182, -0.1006, 1.1187), each
+ *         (m0*R + m1*G) + m2*B, then max(., 0)
+ *   m   = max(max(r, g), b);  s = (1 + m*inv_w2) / (1 + m);
+ *   c   = min(c*s, 1)                   extended Reinhard on max-RGB: a
+ *                                       pixel at peak maps to 1
+ *   out = tout[floor(sqrt(sqrt(c))*4095 + 0.5)]     inverse BT.1886, 2.4
+ * with correctly rounded division and square roots.  The two tables carry
+ * every transcendental step, so no device pow enters the result.
+ *
+ * cc_hdr_tables_build writes the CC_HDR_TABLE_BYTES image the kernels read:
+ * f32 tin[4096], tin[i] = PQ_EOTF(i/4080) nits / reference_white_nits for
+ * i <= 4080 and 0 above, then u8 tout[4096], tout[j] =
+ * floor(255*(j/4095)^(4/2.4) + 0.5); computed in double, rounded once.
+ * Host-only, touches no device.  transfer: CC_HDR_TRANSFER_PQ; anything
+ * else CC_ERR_UNSUPPORTED.  CC_ERR_INVALID on a null pointer or a
+ * reference white that is not positive and finite (BT.2408: 203). */
+enum { CC_HDR_TRANSFER_PQ = 1 };
+#define CC_HDR_TABLE_BYTES 20480
+int cc_hdr_tables_build(int transfer, float reference_white_nits,
+                        void* host_out);
+/* cc_yuv420sp_to_rgb[_resize] with the chain above.  tables_dev: a device
+ * copy of the cc_hdr_tables_build image, 16-byte aligned; inv_w2 =
+ * 1/(peak_nits/reference_white_nits)^2 as f32.  Same arguments, layouts,
+ * alignment rules and checks as the SDR entries; a null or misaligned
+ * tables_dev or an inv_w2 that is negative or not finite is CC_ERR_INVALID
+ * as well, before any launch.  The fused resize converts each of the four taps to u8 by
+ * the full chain before the blend: bit-identical to cc_yuv420sp_hdr_to_rgb
+ * followed by cc_resize_bilinear_u8.  Timed as "yuv420sp_hdr_to_rgb" and
+ * "yuv420sp_hdr_to_rgb_resize". */
+int cc_yuv420sp_hdr_to_rgb(const void* y, const void* uv, int n, int h, int w,
+                           size_t pitch_bytes, int bit_depth, int matrix,
+                           int full_range, const void* tables_dev,
+                           float inv_w2, void* out_rgb, uint64_t stream);
+int cc_yuv420sp_hdr_to_rgb_resize(const void* y, const void* uv, int n,
+                                  int src_h, int src_w, size_t pitch_bytes,
+                                  int bit_depth, int matrix, int full_range,
+                                  const void* tables_dev, float inv_w2,
+                                  void* out_rgb, int out_h, int out_w,
+                                  uint64_t stream);
 /* u8 NHWC bilinear resize (cvcuda LINEAR semantics). */
 int cc_resize_bilinear_u8(const void* in, int n, int src_h, int src_w,
                           void* out, int dst_h, int dst_w, uint64_t stream);

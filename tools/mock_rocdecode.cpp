@@ -13,6 +13,8 @@
 //   MOCK_ROCDEC_BIT_DEPTH   8 | 10 | 12 | ... -> bit_depth_*_minus8
 //   MOCK_ROCDEC_MATRIX      H.273 matrix_coefficients code
 //   MOCK_ROCDEC_FULL_RANGE  0 | 1 -> video_full_range_flag
+//   MOCK_ROCDEC_TRANSFER    H.273 transfer_characteristics code (16 = PQ)
+//   MOCK_ROCDEC_PRIMARIES   H.273 colour_primaries code (9 = BT.2020)
 // The decoder accepts P016 output only for a high-bit-depth stream and NV12
 // only for an 8-bit one; 16-bit surfaces report a pitch of 128 bytes (48
 // u16 samples, padded) with the UV plane pitch x coded height after Y.
@@ -37,6 +39,8 @@ struct MockParser {
   int depth_minus8 = 0;
   int matrix = 0;
   int full_range = 0;
+  int transfer = 0;
+  int primaries = 0;
 };
 
 struct MockDecoder {
@@ -76,6 +80,8 @@ rocDecStatus rocDecCreateVideoParser(RocdecVideoParser* h,
   m->depth_minus8 = env_int("MOCK_ROCDEC_BIT_DEPTH", 8) - 8;
   m->matrix = env_int("MOCK_ROCDEC_MATRIX", 0);
   m->full_range = env_int("MOCK_ROCDEC_FULL_RANGE", 0);
+  m->transfer = env_int("MOCK_ROCDEC_TRANSFER", 0);
+  m->primaries = env_int("MOCK_ROCDEC_PRIMARIES", 0);
   *h = m;
   return ROCDEC_SUCCESS;
 }
@@ -107,6 +113,9 @@ rocDecStatus rocDecParseVideoData(RocdecVideoParser h,
     fmt.bit_depth_chroma_minus8 = (uint8_t)m->depth_minus8;
     fmt.video_signal_description.matrix_coefficients = (uint8_t)m->matrix;
     fmt.video_signal_description.video_full_range_flag = m->full_range & 1;
+    fmt.video_signal_description.transfer_characteristics =
+        (uint8_t)m->transfer;
+    fmt.video_signal_description.color_primaries = (uint8_t)m->primaries;
     int r = m->params.pfn_sequence_callback(m->params.user_data, &fmt);
     if (r == 0) return ROCDEC_RUNTIME_ERROR;
     if (r > 1) m->dpb = r;

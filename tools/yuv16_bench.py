@@ -3,11 +3,14 @@ process: cc_nv12_to_rgb (8-bit) and cc_yuv420sp_to_rgb (10-bit P016) at the
 same full-resolution geometry — one launcher, the u8 and u16 instantiations
 of the same kernels — and cc_nv12_to_rgb_resize at bench.py's own geometry
 (its SRC_H x SRC_W source at pitch SRC_W, 224x224 output, 21 frames x 8
-clips): the first kernel of bench.py's timed region.
+clips): the first kernel of bench.py's timed region.  cc_yuv420sp_hdr_to_rgb
+(10-bit PQ, BT.2020, tone-mapped) runs on the 10-bit leg's own planes, so
+that leg is its yardstick: same bytes moved, plus the chain's arithmetic and
+six table reads per pixel.
 
     python tools/yuv16_bench.py [--frames 8 --height 2160 --width 3840
                                  --launches 30 --warmup 5] [--out LOG]
-                                [--legs all|full|resize]
+                                [--legs all|full|resize|hdr]
 
 Per-launch device time from HIP events around each launch on the current
 stream; prints (and with --out also writes) medians, spread, the achieved
@@ -18,6 +21,10 @@ frame geometry options apply to the two full-resolution legs only.
 moves its time (the unchanged 10-bit kernel differs by ~5 % between a
 process whose 8-bit leg is slow and one whose 8-bit leg is fast), so a
 before/after comparison of one leg runs that leg by itself on both sides.
+--legs hdr alternates the 10-bit SDR leg, the HDR leg and the HDR leg on
+constant planes (every lane reads the same table entries: the chain's
+arithmetic with the table reads taken out of the picture), and prints the
+HDR/SDR ratios beside the SDR leg's own (p90 - p10)/median spread.
 Needs a GPU; there is no fallback.
 """
 
@@ -46,7 +53,7 @@ def main() -> None:
     ap.add_argument("--launches", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--legs", choices=("all", "full", "resize"), default="all")
+    ap.add_argument("--legs", choices=("all", "full", "resize", "hdr"), default="all")
     args = ap.parse_args()
     n, h, w = args.frames, args.height, args.width
 
@@ -61,6 +68,12 @@ def main() -> None:
                          generator=g)
     out8 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
     out16 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    outhdr = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    # mid-grey at 10 bit, MSB-aligned (0x8000 little-endian): one table entry
+    yflat = torch.tensor([0x00, 0x80], dtype=torch.uint8, device=dev).repeat(n, h, w)
+    uvflat = yflat[:, : h // 2].contiguous()
+    tables = hotpath.hdr_tables(hotpath.HDR_TRANSFER_PQ, 203.0)
+    inv_w2 = hotpath.hdr_inv_w2(1000.0, 203.0)
     rn = FRAMES_PER_CLIP * 8
     ry = torch.randint(0, 256, (rn, SRC_H, SRC_W), dtype=torch.uint8, device=dev,
                        generator=g)
@@ -78,19 +91,37 @@ def main() -> None:
             y16.data_ptr(), uv16.data_ptr(), n, h, w, 2 * w, 10, 1, 0,
             out16.data_ptr(), stream))
 
+    def run_hdr() -> None:
+        hotpath.yuv_hdr_to_rgb(
+            y16.data_ptr(), uv16.data_ptr(), n, h, w, 2 * w, outhdr.data_ptr(), stream,
+            tables=tables.data_ptr(), inv_w2=inv_w2, bit_depth=10, matrix=2)
+
+    def run_hdr_flat() -> None:
+        hotpath.yuv_hdr_to_rgb(
+            yflat.data_ptr(), uvflat.data_ptr(), n, h, w, 2 * w, outhdr.data_ptr(),
+            stream, tables=tables.data_ptr(), inv_w2=inv_w2, bit_depth=10, matrix=2)
+
     def run_resize() -> None:
         hotpath.check(lib.cc_nv12_to_rgb_resize(
             ry.data_ptr(), ruv.data_ptr(), rn, SRC_H, SRC_W, SRC_W, rout.data_ptr(),
             RES, RES, stream))
 
     # name -> (launch, bytes the algorithm must move per launch)
+    sdr10, hdr10 = "yuv420sp_to_rgb (10-bit, bt709)", "yuv420sp_hdr_to_rgb (10-bit PQ, bt2020)"
+    hdr10_flat = "yuv420sp_hdr_to_rgb (the same, constant planes)"
     legs = {"nv12_to_rgb (8-bit, bt601)": (run_nv12, n * h * w * 4.5),
-            "yuv420sp_to_rgb (10-bit, bt709)": (run_p010, n * h * w * 6.0),
+            sdr10: (run_p010, n * h * w * 6.0),
+            hdr10: (run_hdr, n * h * w * 6.0),
+            hdr10_flat: (run_hdr_flat, n * h * w * 6.0),
             f"nv12_to_rgb_resize ({rn} x {SRC_H}x{SRC_W} -> {RES}x{RES})":
                 (run_resize, rn * (SRC_H * SRC_W * 1.5 + RES * RES * 3))}
-    if args.legs != "all":
-        legs = {k: v for k, v in legs.items()
-                if ("resize" in k) == (args.legs == "resize")}
+    if args.legs == "hdr":
+        legs = {k: legs[k] for k in (sdr10, hdr10, hdr10_flat)}
+    else:
+        del legs[hdr10_flat]  # a diagnostic of the hdr comparison only
+        if args.legs != "all":
+            legs = {k: v for k, v in legs.items()
+                    if ("resize" in k) == (args.legs == "resize")}
     times: dict[str, list[float]] = {k: [] for k in legs}
     for it in range(args.warmup + args.launches):
         for name, (fn, _) in legs.items():  # alternate the legs
@@ -115,6 +146,15 @@ def main() -> None:
             f"p10 {np.percentile(t, 10):.4f}  p90 {np.percentile(t, 90):.4f}  | "
             f"{nbytes / 1e6:.1f} MB -> {gbs:.0f} GB/s = {gbs / COPY_RATE_GBS:.3f} of "
             f"the {COPY_RATE_GBS / 1000:.2f} TB/s copy rate")
+    if sdr10 in legs and hdr10 in legs:
+        s = np.array(times[sdr10])
+        sm = float(np.median(s))
+        spread = float(np.percentile(s, 90) - np.percentile(s, 10)) / sm
+        for name in (hdr10, hdr10_flat):
+            if name in legs:
+                lines.append(f"{name} / {sdr10}: "
+                             f"{float(np.median(times[name])) / sm:.3f} of the SDR "
+                             f"median; the SDR leg's own (p90 - p10)/median is {spread:.3f}")
     text = "\n".join(lines)
     print(text)
     if args.out:
