@@ -23,16 +23,10 @@
 // multiple of 8 in [64, 128] (so400m 72, ViT-H 80, ViT-g 88, bigG 104,
 // ...).  The MFMA shapes pad it: QK^T runs ceil(HD/32) 16x16x32 k-steps,
 // PV ceil(HD/16) column fragments.  Nothing past column HD of a head is
-// ever read or written — those addresses are the next head, the next
-// Q/K/V section, the next row or past the buffer:
-//   - a fragment chunk is 8 elements at a multiple of 8, so with
-//     HD % 8 == 0 it lies wholly inside or wholly outside [0, HD); an
-//     outside chunk is a zero register (both operands, so the pad
-//     contributes exactly 0 to every score), never a load;
-//   - V^T rows >= HD are written as zeros; they feed only output columns
-//     >= HD, which are never stored.
-// Head offsets are multiples of 16 bytes for every such HD, which keeps
-// the bf16x8 loads legal.  At HD = 64 every pad predicate folds away.
+// ever read or written; the three rungs are sequences of the shared steps
+// below, and the argument is made there, once: every global read goes
+// through load_chunk, every global write through store_o, and stage_vt
+// ties the two together.  At HD = 64 every pad predicate folds away.
 //
 // Numerics (all rungs): f32 accumulation and softmax (matches sdpa's
 // f32 softmax on bf16 inputs); probabilities round to bf16 before PV,
@@ -40,8 +34,6 @@
 // the end-to-end cosine tests.
 
 #include <hip/hip_runtime.h>
-
-#include <vector>
 
 #include "cc_attn_plan.hpp"
 #include "cc_common.hpp"
@@ -51,6 +43,12 @@ namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+// The shared steps take their LDS tiles as LDS pointers.  Through a generic
+// pointer parameter the tile offsets no longer fold into the ds
+// instructions, and k_attn_mid has no registers to spare for them (it
+// spilled: +16 B of scratch per lane at head dim 64, 64 B at 128).
+typedef __attribute__((address_space(3))) __bf16 lds_bf16;
+typedef __attribute__((address_space(3))) bf16x8 lds_bf16x8;
 
 constexpr int SMAX = cc::ATTN_SMALL_MAX;  // padded sequence tile
 constexpr int LD = 72;     // LDS row stride (pad 8 elements vs 64 banks)
@@ -66,6 +64,183 @@ struct HeadDim {
   // columns 64*pass + 16*(t&3) .. +15
   static constexpr int NPASS = (HD + 63) / 64;
 };
+
+// ---- the steps the rungs share ----
+// A wave owns 16 rows of a 64-row tile.  In the 16x16 MFMA accumulator
+// fragments x[n][reg] is (row 4*(lane>>4) + reg, column 16*n + (lane&15))
+// of those 16 rows; the operand fragments are (row lane&15, 8 elements at
+// 8*(lane>>4) of each k-step of 32).
+
+// The 8 elements at head column d of a Q, K or V row inside the sequence
+// (`head_row` points at the head's column 0): loaded if the chunk is inside
+// the head, else a zero register — never a load, because what lies past
+// column HD is the next head, the next Q/K/V section, the next row or past
+// the buffer.  d is a multiple of 8, so with HD % 8 == 0 a chunk lies
+// wholly inside or wholly outside [0, HD).  Zero pad chunks on both MFMA
+// operands add exactly 0 to every score.  Head offsets are multiples of 16
+// bytes for every such HD and the launcher checks the bases, which keeps
+// the 16-byte load legal.  Callers test the row once, around all its
+// chunks: one test per chunk split small's staging loads into six blocks.
+template <int HD>
+__device__ __forceinline__ bf16x8 load_chunk(const __bf16* head_row, int d) {
+  bf16x8 v = {};
+  if (d < HD) v = *(const bf16x8*)(head_row + d);
+  return v;
+}
+
+// Head columns [d0, d0+16) of one V row (two chunks) into column `col` of
+// the transposed image Vt[HDV][LDV].
+template <int LDV>
+__device__ __forceinline__ void store_vt(lds_bf16* Vt, int d0, int col,
+                                         bf16x8 v0, bf16x8 v1) {
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    Vt[(d0 + e) * LDV + col] = v0[e];
+    Vt[(d0 + 8 + e) * LDV + col] = v1[e];
+  }
+}
+
+// One V row into column `col` of Vt: thread t takes head columns 64*pass +
+// 16*(t&3) .. +15 (its row is t>>2, the caller's business).  d0 % 16 == 0,
+// so both chunks lie on one side of HDV.  Rows [HD, HDV) of V^T and dead
+// rows (not loaded) are written as zeros: row d of V^T feeds only output
+// column d, and store_o drops columns >= HD.
+template <int HD, int LDV>
+__device__ __forceinline__ void stage_vt(lds_bf16* Vt, const __bf16* v_row,
+                                         bool live, int col, int tid) {
+#pragma unroll
+  for (int ps = 0; ps < HeadDim<HD>::NPASS; ps++) {
+    const int d0 = 64 * ps + 16 * (tid & 3);
+    if (d0 >= HeadDim<HD>::HDV) continue;
+    bf16x8 v0 = {}, v1 = {};
+    if (live) {
+      v0 = load_chunk<HD>(v_row, d0);
+      v1 = load_chunk<HD>(v_row, d0 + 8);
+    }
+    store_vt<LDV>(Vt, d0, col, v0, v1);
+  }
+}
+
+// S = Q K^T for one wave: query row `qrow`, NFR fragments of key rows from
+// k0, both read directly from global (`qkv + head0` is the head's column 0
+// of the frame's row 0) and clamped to seq-1 — those are masked in the
+// softmax.
+template <int HD, int NFR>
+__device__ __forceinline__ void qk_global(f32x4 (&acc)[NFR],
+                                          const __bf16* qkv, long head0,
+                                          int hidden, int qrow, int k0, int seq,
+                                          int lane) {
+  qrow = qrow < seq ? qrow : seq - 1;
+  const int k0e = 8 * (lane >> 4);
+#pragma unroll
+  for (int kk = 0; kk < HeadDim<HD>::HDK; kk += 32) {
+    const bf16x8 qf = load_chunk<HD>(
+        qkv + head0 + (long)qrow * 3 * hidden, kk + k0e);
+#pragma unroll
+    for (int n = 0; n < NFR; n++) {
+      int krow = k0 + n * 16 + (lane & 15);
+      krow = krow < seq ? krow : seq - 1;
+      const bf16x8 kf = load_chunk<HD>(
+          qkv + head0 + (long)krow * 3 * hidden + hidden, kk + k0e);
+      acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, kf, acc[n], 0, 0, 0);
+    }
+  }
+}
+
+// Row `reg` of NFR score fragments whose column 0 is key `col0 - (lane&15)`:
+// scores scaled, then masked at seq, folded into the running max `mx`; acc
+// becomes exp(score - mx), 0 where masked; returns the row's sum.
+template <int NFR>
+__device__ __forceinline__ float row_exp_sum(f32x4 (&acc)[NFR], int reg,
+                                             float scale, int col0, int seq,
+                                             float& mx) {
+#pragma unroll
+  for (int nn = 0; nn < NFR; nn++) {
+    float s = acc[nn][reg] * scale;
+    if (nn * 16 + col0 >= seq) s = -1e30f;
+    acc[nn][reg] = s;
+    mx = fmaxf(mx, s);
+  }
+#pragma unroll
+  for (int off = 1; off < 16; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+  float sum = 0.0f;
+#pragma unroll
+  for (int nn = 0; nn < NFR; nn++) {
+    float e = __expf(acc[nn][reg] - mx);
+    if (nn * 16 + col0 >= seq) e = 0.0f;
+    acc[nn][reg] = e;
+    sum += e;
+  }
+#pragma unroll
+  for (int off = 1; off < 16; off <<= 1) sum += __shfl_xor(sum, off);
+  return sum;
+}
+
+// Whole-row softmax (the resident rungs): acc becomes the probabilities.
+template <int NFR>
+__device__ __forceinline__ void softmax_rows(f32x4 (&acc)[NFR], float scale,
+                                             int seq, int lane) {
+#pragma unroll
+  for (int reg = 0; reg < 4; reg++) {
+    float mx = -1e30f;
+    const float inv = 1.0f / row_exp_sum(acc, reg, scale, lane & 15, seq, mx);
+#pragma unroll
+    for (int nn = 0; nn < NFR; nn++) acc[nn][reg] = acc[nn][reg] * inv;
+  }
+}
+
+// Probabilities round to bf16 here, into the wave's rows of P[64][LDP].
+template <int NFR, int LDP>
+__device__ __forceinline__ void store_p(lds_bf16* P, const f32x4 (&p)[NFR],
+                                        int row0, int lane) {
+#pragma unroll
+  for (int nn = 0; nn < NFR; nn++)
+#pragma unroll
+    for (int reg = 0; reg < 4; reg++)
+      P[(row0 + reg) * LDP + nn * 16 + (lane & 15)] = (__bf16)p[nn][reg];
+}
+
+// o += P V for the wave's rows over keys [0, KEXT): P[64][LDP] x Vt[HDV][LDP].
+template <int HD, int KEXT, int LDP>
+__device__ __forceinline__ void pv_mfma(f32x4 (&o)[HeadDim<HD>::NF],
+                                        const lds_bf16* P, const lds_bf16* Vt,
+                                        int wid, int lane) {
+  const int j0 = 8 * (lane >> 4);
+#pragma unroll
+  for (int kk = 0; kk < KEXT; kk += 32) {
+    const bf16x8 pf =
+        *(const lds_bf16x8*)(P + (16 * wid + (lane & 15)) * LDP + kk + j0);
+#pragma unroll
+    for (int n = 0; n < HeadDim<HD>::NF; n++) {
+      const bf16x8 vf =
+          *(const lds_bf16x8*)(Vt + (n * 16 + (lane & 15)) * LDP + kk + j0);
+      o[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vf, o[n], 0, 0, 0);
+    }
+  }
+}
+
+// This lane's four O rows, from row `row0` of the frame, divided by l[reg]
+// if DIV.  Rows >= seq and columns >= HD of the last fragment are not
+// stored: those columns are the next head's output or past the row end.
+template <int HD, bool DIV>
+__device__ __forceinline__ void store_o(__bf16* out, long frame, int head,
+                                        int hidden, int seq, int row0, int lane,
+                                        const f32x4 (&o)[HeadDim<HD>::NF],
+                                        const float* l) {
+  const int dcol = lane & 15;
+#pragma unroll
+  for (int nn = 0; nn < HeadDim<HD>::NF; nn++)
+#pragma unroll
+    for (int reg = 0; reg < 4; reg++) {
+      const int row = row0 + reg;
+      if (row < seq && (nn * 16 + 16 <= HD || nn * 16 + dcol < HD)) {
+        float v = o[nn][reg];
+        if constexpr (DIV) v = v / l[reg];
+        out[(frame * seq + row) * (long)hidden + head * HD + nn * 16 + dcol] =
+            (__bf16)v;
+      }
+    }
+}
 
 // NOTE: the direct-global Q/K variant (4 WG/CU) was tried here too and
 // measured SLOWER (89 -> 126 us/launch, profiles/r01_rocprof_b32_afterfusions.txt)
@@ -89,77 +264,48 @@ __global__ __launch_bounds__(256, 2) void k_attn_small(
   __shared__ __bf16 lds[2 * SMAX * LDQ + (G::HDV + SMAX) * LD];
   __bf16* Q = lds;
   __bf16* K = lds + SMAX * LDQ;
-  __bf16* Vt = lds + 2 * SMAX * LDQ;
-  __bf16* P = Vt + G::HDV * LD;
+  lds_bf16* Vt = (lds_bf16*)lds + 2 * SMAX * LDQ;
+  lds_bf16* P = Vt + G::HDV * LD;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;  // 4 waves; wave w owns S rows [16w, 16w+16)
+  const int rb = 16 * wid + 4 * (lane >> 4);  // first accumulator row
 
-  // ---- load Q/K/V tiles: thread t handles row t>>2, cols (t&3)*16.. ----
+  // ---- stage Q, K and V^T: thread t -> row t>>2, 16 head columns per
+  // pass, as stage_vt (d0 % 16 == 0, so both chunks lie on one side of HDK
+  // and of HDV <= HDK).  A pass issues its six loads together, ahead of
+  // its LDS stores: taken one by one behind them they cost 18 % at seq 50.
   {
     const int row = tid >> 2;
-    const int d0 = (tid & 3) * 16;
-    const long base = ((frame * seq + row) * 3) * (long)hidden + (long)head * HD;
-    bf16x8 z = {};
-    bf16x8 q0 = z, q1 = z, k0 = z, k1 = z, v0 = z, v1 = z;
-    if (row < seq) {
-      q0 = *(const bf16x8*)(qkv + base + d0);
-      q1 = *(const bf16x8*)(qkv + base + d0 + 8);
-      k0 = *(const bf16x8*)(qkv + base + hidden + d0);
-      k1 = *(const bf16x8*)(qkv + base + hidden + d0 + 8);
-      v0 = *(const bf16x8*)(qkv + base + 2 * hidden + d0);
-      v1 = *(const bf16x8*)(qkv + base + 2 * hidden + d0 + 8);
-    }
-    *(bf16x8*)(Q + row * LDQ + d0) = q0;
-    *(bf16x8*)(Q + row * LDQ + d0 + 8) = q1;
-    *(bf16x8*)(K + row * LDQ + d0) = k0;
-    *(bf16x8*)(K + row * LDQ + d0 + 8) = k1;
-    // V transposed: Vt[d][row] = V[row][d]
+    const bool live = row < seq;
+    const __bf16* src =
+        qkv + ((frame * seq + row) * 3) * (long)hidden + (long)head * HD;
 #pragma unroll
-    for (int e = 0; e < 8; e++) {
-      Vt[(d0 + e) * LD + row] = v0[e];
-      Vt[(d0 + 8 + e) * LD + row] = v1[e];
-    }
-  }
-  // ---- head dims above 64: columns 64 + (t&3)*16.. of the same row.  A
-  // chunk inside the head is loaded, one outside stays zero; d0 % 16 == 0,
-  // so both chunks lie on one side of HDK (Q/K extent) and of HDV (Vt
-  // rows) ----
-  if constexpr (HD > 64) {
-    const int row = tid >> 2;
-    const int d0 = 64 + (tid & 3) * 16;
-    const long base = ((frame * seq + row) * 3) * (long)hidden + (long)head * HD;
-    bf16x8 z = {};
-    bf16x8 q0 = z, q1 = z, k0 = z, k1 = z, v0 = z, v1 = z;
-    if (row < seq && d0 < HD) {
-      q0 = *(const bf16x8*)(qkv + base + d0);
-      k0 = *(const bf16x8*)(qkv + base + hidden + d0);
-      v0 = *(const bf16x8*)(qkv + base + 2 * hidden + d0);
-    }
-    if (row < seq && d0 + 8 < HD) {
-      q1 = *(const bf16x8*)(qkv + base + d0 + 8);
-      k1 = *(const bf16x8*)(qkv + base + hidden + d0 + 8);
-      v1 = *(const bf16x8*)(qkv + base + 2 * hidden + d0 + 8);
-    }
-    if (d0 < G::HDK) {
-      *(bf16x8*)(Q + row * LDQ + d0) = q0;
-      *(bf16x8*)(Q + row * LDQ + d0 + 8) = q1;
-      *(bf16x8*)(K + row * LDQ + d0) = k0;
-      *(bf16x8*)(K + row * LDQ + d0 + 8) = k1;
-    }
-    if (d0 < G::HDV) {
+    for (int ps = 0; ps < G::NPASS; ps++) {
+      const int d0 = 64 * ps + 16 * (tid & 3);
+      if (d0 >= G::HDK) continue;
+      bf16x8 q[2] = {}, k[2] = {}, v[2] = {};
+      if (live) {
 #pragma unroll
-      for (int e = 0; e < 8; e++) {
-        Vt[(d0 + e) * LD + row] = v0[e];
-        Vt[(d0 + 8 + e) * LD + row] = v1[e];
+        for (int c = 0; c < 2; c++) {
+          q[c] = load_chunk<HD>(src, d0 + 8 * c);
+          k[c] = load_chunk<HD>(src + hidden, d0 + 8 * c);
+          v[c] = load_chunk<HD>(src + 2 * hidden, d0 + 8 * c);
+        }
       }
+#pragma unroll
+      for (int c = 0; c < 2; c++) {
+        *(bf16x8*)(Q + row * LDQ + d0 + 8 * c) = q[c];
+        *(bf16x8*)(K + row * LDQ + d0 + 8 * c) = k[c];
+      }
+      if (d0 < G::HDV) store_vt<LD>(Vt, d0, row, v[0], v[1]);
     }
   }
   __syncthreads();
 
-  // ---- S = Q K^T * scale, rows [16w,16w+16), cols 0..63 ----
-  f32x4 acc[4] = {};
+  // ---- S = Q K^T, rows [16w,16w+16), cols 0..63 ----
+  f32x4 acc[SMAX / 16] = {};
   {
     const int qrow = 16 * wid + (lane & 15);
     const int k0e = 8 * (lane >> 4);
@@ -167,89 +313,19 @@ __global__ __launch_bounds__(256, 2) void k_attn_small(
     for (int kk = 0; kk < G::HDK; kk += 32) {
       bf16x8 qf = *(const bf16x8*)(Q + qrow * LDQ + kk + k0e);
 #pragma unroll
-      for (int n = 0; n < 4; n++) {
+      for (int n = 0; n < SMAX / 16; n++) {
         bf16x8 kf = *(const bf16x8*)(K + (n * 16 + (lane & 15)) * LDQ + kk + k0e);
         acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, kf, acc[n], 0, 0, 0);
       }
     }
   }
-
-  // ---- masked, scaled softmax over cols (per row) ----
-  // acc value (row = 16w + (lane>>4)*4 + reg, col = n*16 + lane&15)
-  float pr[4][4];  // probabilities, same layout
-  {
-    const int colr = lane & 15;
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) {
-      float mx = -1e30f;
-      float sv[4];
-#pragma unroll
-      for (int nn = 0; nn < 4; nn++) {
-        float s = acc[nn][reg] * scale;
-        if (nn * 16 + colr >= seq) s = -1e30f;
-        sv[nn] = s;
-        mx = fmaxf(mx, s);
-      }
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1)
-        mx = fmaxf(mx, __shfl_xor(mx, off));
-      float sum = 0.0f;
-#pragma unroll
-      for (int nn = 0; nn < 4; nn++) {
-        float e = __expf(sv[nn] - mx);
-        if (nn * 16 + colr >= seq) e = 0.0f;
-        sv[nn] = e;
-        sum += e;
-      }
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) sum += __shfl_xor(sum, off);
-      const float inv = 1.0f / sum;
-#pragma unroll
-      for (int nn = 0; nn < 4; nn++) pr[nn][reg] = sv[nn] * inv;
-    }
-  }
-  // write P (bf16) to LDS for the PV matmul
-  {
-    const int colr = lane & 15;
-    const int rbase = 16 * wid + 4 * (lane >> 4);
-#pragma unroll
-    for (int nn = 0; nn < 4; nn++)
-#pragma unroll
-      for (int reg = 0; reg < 4; reg++)
-        P[(rbase + reg) * LD + nn * 16 + colr] = (__bf16)pr[nn][reg];
-  }
+  softmax_rows(acc, scale, seq, lane);
+  store_p<SMAX / 16, LD>(P, acc, rb, lane);
   __syncthreads();
 
-  // ---- O = P Vt^T : rows [16w,16w+16) of O, cols d = 0..HDV-1 ----
   f32x4 oacc[G::NF] = {};
-  {
-    const int prow = 16 * wid + (lane & 15);
-    const int j0 = 8 * (lane >> 4);
-#pragma unroll
-    for (int kk = 0; kk < SMAX; kk += 32) {
-      bf16x8 pf = *(const bf16x8*)(P + prow * LD + kk + j0);
-#pragma unroll
-      for (int n = 0; n < G::NF; n++) {
-        bf16x8 vf = *(const bf16x8*)(Vt + (n * 16 + (lane & 15)) * LD + kk + j0);
-        oacc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vf, oacc[n], 0, 0, 0);
-      }
-    }
-  }
-  // ---- store O: (row = 16w + (lane>>4)*4 + reg, d = n*16 + lane&15);
-  // columns >= HD of the last fragment belong to the next head ----
-  {
-    const int dcol = lane & 15;
-    const int rbase = 16 * wid + 4 * (lane >> 4);
-#pragma unroll
-    for (int nn = 0; nn < G::NF; nn++)
-#pragma unroll
-      for (int reg = 0; reg < 4; reg++) {
-        const int row = rbase + reg;
-        if (row < seq && (nn * 16 + 16 <= HD || nn * 16 + dcol < HD))
-          out[(frame * seq + row) * (long)hidden + head * HD + nn * 16 + dcol] =
-              (__bf16)oacc[nn][reg];
-      }
-  }
+  pv_mfma<HD, SMAX, LD>(oacc, P, Vt, wid, lane);
+  store_o<HD, false>(out, frame, head, hidden, seq, rb, lane, oacc, nullptr);
 }
 
 
@@ -278,60 +354,22 @@ __global__ __launch_bounds__(256, 2) void k_attn_mid(
   if (frame >= n_frames) return;
 
   __shared__ __bf16 lds[(G::HDV + 64) * LDM];
-  __bf16* Vt = lds;                  // [HDV][LDM] rows d, cols s
-  __bf16* P = lds + G::HDV * LDM;    // [64][LDM] rows q, cols s
+  lds_bf16* Vt = (lds_bf16*)lds;     // [HDV][LDM] rows d, cols s
+  lds_bf16* P = Vt + G::HDV * LDM;   // [64][LDM] rows q, cols s
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;
+  const int rb = 16 * wid + 4 * (lane >> 4);  // first accumulator row
   const long qkv_base = (frame * (long)seq * 3) * hidden + (long)head * HD;
 
-  // ---- V^T load: 64 rows per pass, thread t -> row t>>2, d (t&3)*16
-  {
-    const int row = tid >> 2;
-    const int d0 = (tid & 3) * 16;
+  // ---- V^T: all SMID rows, 64 per step, thread t -> row t>>2
 #pragma unroll
-    for (int j = 0; j < SMID / 64 + 1; j++) {
-      const int r = j * 64 + row;
-      if (r >= SMID) break;
-      bf16x8 z = {};
-      bf16x8 v0 = z, v1 = z;
-      if (r < seq) {
-        const long base = qkv_base + (long)r * 3 * hidden + 2 * hidden;
-        v0 = *(const bf16x8*)(qkv + base + d0);
-        v1 = *(const bf16x8*)(qkv + base + d0 + 8);
-      }
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        Vt[(d0 + e) * LDM + r] = v0[e];
-        Vt[(d0 + 8 + e) * LDM + r] = v1[e];
-      }
-    }
-  }
-  // ---- head dims above 64: d 64 + (t&3)*16.. of the same rows; chunks
-  // past HD are zero rows of V^T, rows past HDV are not held
-  if constexpr (HD > 64) {
-    const int row = tid >> 2;
-    const int d0 = 64 + (tid & 3) * 16;
-    if (d0 < G::HDV) {
-#pragma unroll
-      for (int j = 0; j < SMID / 64 + 1; j++) {
-        const int r = j * 64 + row;
-        if (r >= SMID) break;
-        bf16x8 z = {};
-        bf16x8 v0 = z, v1 = z;
-        if (r < seq) {
-          const long base = qkv_base + (long)r * 3 * hidden + 2 * hidden;
-          if (d0 < HD) v0 = *(const bf16x8*)(qkv + base + d0);
-          if (d0 + 8 < HD) v1 = *(const bf16x8*)(qkv + base + d0 + 8);
-        }
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-          Vt[(d0 + e) * LDM + r] = v0[e];
-          Vt[(d0 + 8 + e) * LDM + r] = v1[e];
-        }
-      }
-    }
+  for (int j = 0; j < SMID / 64 + 1; j++) {
+    const int r = j * 64 + (tid >> 2);
+    if (r >= SMID) break;
+    stage_vt<HD, LDM>(Vt, qkv + qkv_base + (long)r * 3 * hidden + 2 * hidden,
+                      r < seq, r, tid);
   }
 
   const int n_qtiles = (seq + 63) / 64;
@@ -339,109 +377,19 @@ __global__ __launch_bounds__(256, 2) void k_attn_mid(
     const int q0 = qt * 64;
     __syncthreads();  // Vt ready (first iter); P free (later iters)
 
-    // ---- S = Q K^T: wave rows [16*wid, +16), 18 col frags; Q/K frags
-    // read directly from global (16B contiguous), rows clamped to seq-1
-    // (masked in softmax anyway); chunks past HD are zero, not loaded.
     f32x4 acc[SMID / 16];
 #pragma unroll
     for (int n = 0; n < SMID / 16; n++) acc[n] = f32x4{};
-    {
-      int qrow = q0 + 16 * wid + (lane & 15);
-      qrow = qrow < seq ? qrow : seq - 1;
-      const int k0e = 8 * (lane >> 4);
-#pragma unroll
-      for (int kk = 0; kk < G::HDK; kk += 32) {
-        const bool in = kk + 32 <= HD || kk + k0e < HD;
-        bf16x8 qf = {};
-        if (in)
-          qf = *(const bf16x8*)(qkv + qkv_base + (long)qrow * 3 * hidden + kk +
-                                k0e);
-#pragma unroll
-        for (int n = 0; n < SMID / 16; n++) {
-          int krow = n * 16 + (lane & 15);
-          krow = krow < seq ? krow : seq - 1;
-          bf16x8 kf = {};
-          if (in)
-            kf = *(const bf16x8*)(qkv + qkv_base + (long)krow * 3 * hidden +
-                                  hidden + kk + k0e);
-          acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, kf, acc[n], 0, 0, 0);
-        }
-      }
-    }
-
-    // ---- softmax per row (cols masked at seq)
-    {
-      const int colr = lane & 15;
-#pragma unroll
-      for (int reg = 0; reg < 4; reg++) {
-        float mx = -1e30f;
-        float sv[SMID / 16];
-#pragma unroll
-        for (int nn = 0; nn < SMID / 16; nn++) {
-          float sc = acc[nn][reg] * scale;
-          if (nn * 16 + colr >= seq) sc = -1e30f;
-          sv[nn] = sc;
-          mx = fmaxf(mx, sc);
-        }
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1)
-          mx = fmaxf(mx, __shfl_xor(mx, off));
-        float sum = 0.0f;
-#pragma unroll
-        for (int nn = 0; nn < SMID / 16; nn++) {
-          float e = __expf(sv[nn] - mx);
-          if (nn * 16 + colr >= seq) e = 0.0f;
-          sv[nn] = e;
-          sum += e;
-        }
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1) sum += __shfl_xor(sum, off);
-        const float inv = 1.0f / sum;
-#pragma unroll
-        for (int nn = 0; nn < SMID / 16; nn++) acc[nn][reg] = sv[nn] * inv;
-      }
-    }
-    // ---- P to LDS (bf16)
-    {
-      const int colr = lane & 15;
-      const int rbase = 16 * wid + 4 * (lane >> 4);
-#pragma unroll
-      for (int nn = 0; nn < SMID / 16; nn++)
-#pragma unroll
-        for (int reg = 0; reg < 4; reg++)
-          P[(rbase + reg) * LDM + nn * 16 + colr] = (__bf16)acc[nn][reg];
-    }
+    qk_global<HD>(acc, qkv, qkv_base, hidden, q0 + 16 * wid + (lane & 15), 0,
+                  seq, lane);
+    softmax_rows(acc, scale, seq, lane);
+    store_p<SMID / 16, LDM>(P, acc, rb, lane);
     __syncthreads();
 
-    // ---- O = P V : rows [16*wid,+16), d cols 0..HDV-1
     f32x4 oacc[G::NF] = {};
-    {
-      const int prow = 16 * wid + (lane & 15);
-      const int j0 = 8 * (lane >> 4);
-#pragma unroll
-      for (int kk = 0; kk < SMID; kk += 32) {
-        bf16x8 pf = *(const bf16x8*)(P + prow * LDM + kk + j0);
-#pragma unroll
-        for (int n = 0; n < G::NF; n++) {
-          bf16x8 vf =
-              *(const bf16x8*)(Vt + (n * 16 + (lane & 15)) * LDM + kk + j0);
-          oacc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vf, oacc[n], 0, 0, 0);
-        }
-      }
-    }
-    {
-      const int dcol = lane & 15;
-      const int rbase = 16 * wid + 4 * (lane >> 4);
-#pragma unroll
-      for (int nn = 0; nn < G::NF; nn++)
-#pragma unroll
-        for (int reg = 0; reg < 4; reg++) {
-          const int row = q0 + rbase + reg;
-          if (row < seq && (nn * 16 + 16 <= HD || nn * 16 + dcol < HD))
-            out[(frame * seq + row) * (long)hidden + head * HD + nn * 16 +
-                dcol] = (__bf16)oacc[nn][reg];
-        }
-    }
+    pv_mfma<HD, SMID, LDM>(oacc, P, Vt, wid, lane);
+    store_o<HD, false>(out, frame, head, hidden, seq, q0 + rb, lane, oacc,
+                       nullptr);
   }
 }
 
@@ -473,17 +421,17 @@ __global__ __launch_bounds__(256, 2) void k_attn_flash(
   if (frame >= n_frames) return;
 
   __shared__ __bf16 lds[(G::HDV + 64) * LDF];
-  __bf16* Vt = lds;                  // [HDV d][LDF s]
-  __bf16* P = lds + G::HDV * LDF;    // [64 q][LDF s]
+  lds_bf16* Vt = (lds_bf16*)lds;     // [HDV d][LDF s]
+  lds_bf16* P = Vt + G::HDV * LDF;   // [64 q][LDF s]
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;
+  const int rb = 16 * wid + 4 * (lane >> 4);  // first accumulator row
   const long qkv_base = (frame * (long)seq * 3) * hidden + (long)head * HD;
   const int q0 = qt * 64;
 
-  // per-lane row state (rows rbase..rbase+3 of this wave's 16)
-  const int rbase_l = 4 * (lane >> 4);
+  // per-lane row state (rows 4*(lane>>4) + reg of this wave's 16)
   float m_run[4], l_run[4];
   f32x4 oacc[G::NF] = {};
 #pragma unroll
@@ -495,119 +443,35 @@ __global__ __launch_bounds__(256, 2) void k_attn_flash(
   const int n_kv = (seq + FKV - 1) / FKV;
   for (int kt = 0; kt < n_kv; kt++) {
     const int k0 = kt * FKV;
-    // ---- V^T tile into LDS (thread t -> row t>>2, d (t&3)*16, +64 per
-    // head-dim pass; chunks past HD are zero rows of V^T)
     __syncthreads();  // P/Vt free from the previous tile
-#pragma unroll
-    for (int ps = 0; ps < G::NPASS; ps++) {
-      const int row = tid >> 2;
-      const int d0 = (tid & 3) * 16 + 64 * ps;
-      if (d0 >= G::HDV) continue;
-      const bool in0 = d0 < HD, in1 = d0 + 8 < HD;
-      bf16x8 z = {};
-      bf16x8 v0 = z, v1 = z;
-      if (k0 + row < seq) {
-        const long base = qkv_base + (long)(k0 + row) * 3 * hidden + 2 * hidden;
-        if (in0) v0 = *(const bf16x8*)(qkv + base + d0);
-        if (in1) v1 = *(const bf16x8*)(qkv + base + d0 + 8);
-      }
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        Vt[(d0 + e) * LDF + row] = v0[e];
-        Vt[(d0 + 8 + e) * LDF + row] = v1[e];
-      }
-    }
-
-    // ---- S tile = Q K^T (wave rows, 4 col frags), direct global Q/K;
-    // chunks past HD are zero, not loaded
-    f32x4 acc[4] = {};
+    // ---- V^T tile: thread t -> row k0 + (t>>2)
     {
-      int qrow = q0 + 16 * wid + (lane & 15);
-      qrow = qrow < seq ? qrow : seq - 1;
-      const int k0e = 8 * (lane >> 4);
-#pragma unroll
-      for (int kk = 0; kk < G::HDK; kk += 32) {
-        const bool in = kk + 32 <= HD || kk + k0e < HD;
-        bf16x8 qf = {};
-        if (in)
-          qf = *(const bf16x8*)(qkv + qkv_base + (long)qrow * 3 * hidden + kk +
-                                k0e);
-#pragma unroll
-        for (int n = 0; n < 4; n++) {
-          int krow = k0 + n * 16 + (lane & 15);
-          krow = krow < seq ? krow : seq - 1;
-          bf16x8 kf = {};
-          if (in)
-            kf = *(const bf16x8*)(qkv + qkv_base + (long)krow * 3 * hidden +
-                                  hidden + kk + k0e);
-          acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, kf, acc[n], 0, 0, 0);
-        }
-      }
+      const int r = k0 + (tid >> 2);
+      stage_vt<HD, LDF>(Vt, qkv + qkv_base + (long)r * 3 * hidden + 2 * hidden,
+                        r < seq, tid >> 2, tid);
     }
 
-    // ---- online softmax update (per row)
+    f32x4 acc[FKV / 16] = {};
+    qk_global<HD>(acc, qkv, qkv_base, hidden, q0 + 16 * wid + (lane & 15), k0,
+                  seq, lane);
+
+    // ---- online softmax update (per row); acc: unnormalized probabilities
     float alpha[4];
-    {
-      const int colr = lane & 15;
 #pragma unroll
-      for (int reg = 0; reg < 4; reg++) {
-        float mx = m_run[reg];
-        float sv[4];
-#pragma unroll
-        for (int nn = 0; nn < 4; nn++) {
-          float sc = acc[nn][reg] * scale;
-          if (k0 + nn * 16 + colr >= seq) sc = -1e30f;
-          sv[nn] = sc;
-          mx = fmaxf(mx, sc);
-        }
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1)
-          mx = fmaxf(mx, __shfl_xor(mx, off));
-        alpha[reg] = __expf(m_run[reg] - mx);
-        float sum = 0.0f;
-#pragma unroll
-        for (int nn = 0; nn < 4; nn++) {
-          float e = __expf(sv[nn] - mx);
-          if (k0 + nn * 16 + colr >= seq) e = 0.0f;
-          sv[nn] = e;
-          sum += e;
-        }
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1) sum += __shfl_xor(sum, off);
-        l_run[reg] = l_run[reg] * alpha[reg] + sum;
-        m_run[reg] = mx;
-#pragma unroll
-        for (int nn = 0; nn < 4; nn++) acc[nn][reg] = sv[nn];
-      }
+    for (int reg = 0; reg < 4; reg++) {
+      float mx = m_run[reg];
+      const float sum =
+          row_exp_sum(acc, reg, scale, k0 + (lane & 15), seq, mx);
+      alpha[reg] = __expf(m_run[reg] - mx);
+      l_run[reg] = l_run[reg] * alpha[reg] + sum;
+      m_run[reg] = mx;
     }
-    // ---- P tile to LDS (unnormalized probabilities, bf16)
-    {
-      const int colr = lane & 15;
-      const int rb = 16 * wid + rbase_l;
-#pragma unroll
-      for (int nn = 0; nn < 4; nn++)
-#pragma unroll
-        for (int reg = 0; reg < 4; reg++)
-          P[(rb + reg) * LDF + nn * 16 + colr] = (__bf16)acc[nn][reg];
-    }
+    store_p<FKV / 16, LDF>(P, acc, rb, lane);
     __syncthreads();
 
     // ---- O = alpha * O + P V
     f32x4 pv[G::NF] = {};
-    {
-      const int prow = 16 * wid + (lane & 15);
-      const int j0 = 8 * (lane >> 4);
-#pragma unroll
-      for (int kk = 0; kk < FKV; kk += 32) {
-        bf16x8 pf = *(const bf16x8*)(P + prow * LDF + kk + j0);
-#pragma unroll
-        for (int n = 0; n < G::NF; n++) {
-          bf16x8 vf =
-              *(const bf16x8*)(Vt + (n * 16 + (lane & 15)) * LDF + kk + j0);
-          pv[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vf, pv[n], 0, 0, 0);
-        }
-      }
-    }
+    pv_mfma<HD, FKV, LDF>(pv, P, Vt, wid, lane);
 #pragma unroll
     for (int n = 0; n < G::NF; n++)
 #pragma unroll
@@ -615,20 +479,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_flash(
         oacc[n][reg] = oacc[n][reg] * alpha[reg] + pv[n][reg];
   }
 
-  // ---- store O / l (columns >= HD of the last fragment: next head's)
-  {
-    const int dcol = lane & 15;
-    const int rb = 16 * wid + rbase_l;
-#pragma unroll
-    for (int nn = 0; nn < G::NF; nn++)
-#pragma unroll
-      for (int reg = 0; reg < 4; reg++) {
-        const int row = q0 + rb + reg;
-        if (row < seq && (nn * 16 + 16 <= HD || nn * 16 + dcol < HD))
-          out[(frame * seq + row) * (long)hidden + head * HD + nn * 16 + dcol] =
-              (__bf16)(oacc[nn][reg] / l_run[reg]);
-      }
-  }
+  store_o<HD, true>(out, frame, head, hidden, seq, q0 + rb, lane, oacc, l_run);
 }
 
 // ---- CLS-query variant: one query row per (frame, head) ----

@@ -25,7 +25,7 @@ from cosmos_curate_amd import hotpath
 pytestmark = pytest.mark.gpu
 
 N, HEADS = 2, 3
-HDS = [72, 80, 88, 96, 104, 128]
+HDS = [64, 72, 80, 88, 96, 104, 112, 120, 128]
 
 
 @pytest.fixture(scope="module")
