@@ -68,7 +68,8 @@ __device__ __forceinline__ unsigned short f32_to_bf16_rne(float v) {
   return (unsigned short)((cv.u + 0x7fffu + lsb) >> 16);
 }
 
-// fused activations (quick-gelu / SigLIP tanh-gelu; see epilogue notes)
+// fused activations (quick-gelu / SigLIP tanh-gelu / InternVideo2 erf-gelu;
+// see epilogue notes)
 template <int ACT>
 __device__ __forceinline__ float cc_act(float v) {
   if constexpr (ACT == 1)
@@ -80,6 +81,8 @@ __device__ __forceinline__ float cc_act(float v) {
     float t = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * z) + 1.0f);
     return 0.5f * v * (1.0f + t);
   }
+  if constexpr (ACT == 3)  // exact (erf) gelu: torch gelu(approximate="none")
+    return 0.5f * v * (1.0f + erff(v * 0.70710678f));
   return v;
 }
 
@@ -748,25 +751,41 @@ void gemm_run(const cc_gemm_plan_info& p, const GemmArgs& g) {
 }
 
 using GemmRunFn = void (*)(const cc_gemm_plan_info&, const GemmArgs&);
-constexpr GemmRunFn kGemmRun[3][2][2] = {  // [act][has_bias][has_residual]
+// a null entry is a combination that is not instantiated: erf-gelu (act 3)
+// exists with a bias and no residual only, what an fc1 needs
+constexpr GemmRunFn kGemmRun[4][2][2] = {  // [act][has_bias][has_residual]
     {{gemm_run<0, false, false>, gemm_run<0, false, true>},
      {gemm_run<0, true, false>, gemm_run<0, true, true>}},
     {{gemm_run<1, false, false>, gemm_run<1, false, true>},
      {gemm_run<1, true, false>, gemm_run<1, true, true>}},
     {{gemm_run<2, false, false>, gemm_run<2, false, true>},
-     {gemm_run<2, true, false>, gemm_run<2, true, true>}}};
-// folded-LayerNorm consumers: bias (= W beta + b) always, no residual
-constexpr GemmRunFn kGemmRunLn[3] = {  // [act]
+     {gemm_run<2, true, false>, gemm_run<2, true, true>}},
+    {{nullptr, nullptr}, {gemm_run<3, true, false>, nullptr}}};
+// folded-norm consumers: bias (= W beta + b) always, no residual
+constexpr GemmRunFn kGemmRunLn[4] = {  // [act]
     gemm_run<0, true, false, true>, gemm_run<1, true, false, true>,
-    gemm_run<2, true, false, true>};
+    gemm_run<2, true, false, true>, gemm_run<3, true, false, true>};
 
-// act: 1 quick-gelu, 2 tanh-gelu (SigLIP), anything else none
-int act_index(int act) { return act == 1 ? 1 : act == 2 ? 2 : 0; }
+// act: 0 none, 1 quick-gelu, 2 tanh-gelu (SigLIP), 3 erf-gelu
+// (InternVideo2); no other value is taken
+int check_act(int act) {
+  if (act < 0 || act > 3)
+    return cc::set_error(CC_ERR_INVALID,
+                         "gemm act must be 0 (none), 1 (quick-gelu), 2 "
+                         "(tanh-gelu) or 3 (erf-gelu), got %d", act);
+  return CC_OK;
+}
 
 int gemm_launch(const void* A, int64_t lda, const void* B, void* C, int64_t M,
                 int64_t N, int64_t K, const float* bias, int c_dtype, int act,
                 const void* residual, int64_t ldr, uint64_t stream) {
   if (!A || !B || !C) return cc::set_error(CC_ERR_INVALID, "bad gemm args");
+  if (int rc = check_act(act)) return rc;
+  const GemmRunFn run = kGemmRun[act][bias != nullptr][residual != nullptr];
+  if (!run)
+    return cc::set_error(CC_ERR_UNSUPPORTED,
+                         "gemm act %d is instantiated with a bias and "
+                         "without a residual only", act);
   cc_gemm_plan_info plan;
   if (int rc = cc::gemm_plan(M, N, K, lda, ldr, bias != nullptr, act,
                              residual != nullptr, cc::gemm_env_knobs(), &plan))
@@ -775,8 +794,37 @@ int gemm_launch(const void* A, int64_t lda, const void* B, void* C, int64_t M,
                       (const __bf16*)residual, (long)M, (long)N, (long)K,
                       (long)lda, (long)ldr, c_dtype == 1 ? 1 : 0,
                       (hipStream_t)stream};
+  return cc::timed_launch("gemm_bf16", stream, [&] { run(plan, args); });
+}
+
+// cc_gemm_bf16_ln / cc_gemm_bf16_rms: the finalize kernel of the norm,
+// then the LN_IN GEMM on the (mean, rstd) pairs it wrote
+int gemm_norm_in(bool rms, const void* A, int64_t row_step, const void* stats,
+                 void* murstd, const void* Wfold, const float* colsum,
+                 const float* cbias, void* C, int64_t M, int64_t N, int64_t K,
+                 int act, float eps, uint64_t stream) {
+  if (!A || !stats || !murstd || !Wfold || !colsum || !cbias || !C ||
+      row_step <= 0)
+    return cc::set_error(CC_ERR_INVALID, "bad gemm_ln args");
+  if (int rc = check_act(act)) return rc;
+  if (!cc::ln_h_supported(K))
+    return cc::set_error(CC_ERR_UNSUPPORTED,
+                         "gemm_ln: no LayerNorm statistics at K %lld",
+                         (long long)K);
+  cc_gemm_plan_info plan;
+  if (int rc = cc::gemm_plan(M, N, K, row_step * K, N, true, act, false,
+                             cc::gemm_env_knobs(), &plan))
+    return rc;
+  if (int rc = rms ? cc_rms_finalize(stats, M, K, row_step, eps, murstd, stream)
+                   : cc_ln_finalize(stats, M, K, row_step, eps, murstd, stream))
+    return rc;
+  GemmArgs args{(const __bf16*)A, (const __bf16*)Wfold, C, cbias, nullptr,
+                (long)M, (long)N, (long)K, (long)(row_step * K), (long)N, 1,
+                (hipStream_t)stream};
+  args.colsum = colsum;
+  args.murstd = (const float2*)murstd;
   return cc::timed_launch("gemm_bf16", stream, [&] {
-    kGemmRun[act_index(act)][bias != nullptr][residual != nullptr](plan, args);
+    kGemmRunLn[act](plan, args);
   });
 }
 }  // namespace
@@ -848,25 +896,16 @@ extern "C" int cc_gemm_bf16_ln(const void* A, int64_t row_step,
                                const float* cbias, void* C, int64_t M,
                                int64_t N, int64_t K, int act, float eps,
                                uint64_t stream) {
-  if (!A || !stats || !murstd || !Wfold || !colsum || !cbias || !C ||
-      row_step <= 0)
-    return cc::set_error(CC_ERR_INVALID, "bad gemm_ln args");
-  if (!cc::ln_h_supported(K))
-    return cc::set_error(CC_ERR_UNSUPPORTED,
-                         "gemm_ln: no LayerNorm statistics at K %lld",
-                         (long long)K);
-  cc_gemm_plan_info plan;
-  if (int rc = cc::gemm_plan(M, N, K, row_step * K, N, true, act, false,
-                             cc::gemm_env_knobs(), &plan))
-    return rc;
-  if (int rc = cc_ln_finalize(stats, M, K, row_step, eps, murstd, stream))
-    return rc;
-  GemmArgs args{(const __bf16*)A, (const __bf16*)Wfold, C, cbias, nullptr,
-                (long)M, (long)N, (long)K, (long)(row_step * K), (long)N, 1,
-                (hipStream_t)stream};
-  args.colsum = colsum;
-  args.murstd = (const float2*)murstd;
-  return cc::timed_launch("gemm_bf16", stream, [&] {
-    kGemmRunLn[act_index(act)](plan, args);
-  });
+  return gemm_norm_in(false, A, row_step, stats, murstd, Wfold, colsum, cbias,
+                      C, M, N, K, act, eps, stream);
+}
+
+extern "C" int cc_gemm_bf16_rms(const void* A, int64_t row_step,
+                                const void* stats, void* murstd,
+                                const void* Wfold, const float* colsum,
+                                const float* cbias, void* C, int64_t M,
+                                int64_t N, int64_t K, int act, float eps,
+                                uint64_t stream) {
+  return gemm_norm_in(true, A, row_step, stats, murstd, Wfold, colsum, cbias,
+                      C, M, N, K, act, eps, stream);
 }

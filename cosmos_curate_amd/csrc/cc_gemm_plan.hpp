@@ -125,8 +125,8 @@ inline int gemm_plan(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldr,
   // profiles/r02_epi_ab.log), scalar for bare C=A*B^T launches where the
   // 4-pass staging is pure overhead (bare fc1 928 scalar vs 825 staged,
   // profiles/r02_gemm_v20.log).  f32 outputs always store scalar.
-  // (act: 1 quick-gelu, 2 tanh-gelu, anything else none.)
-  p->epi_staged = (has_bias || has_residual || act == 1 || act == 2) ? 1 : 0;
+  // (act: 0 none, 1 quick-gelu, 2 tanh-gelu, 3 erf-gelu.)
+  p->epi_staged = (has_bias || has_residual || (act >= 1 && act <= 3)) ? 1 : 0;
   return CC_OK;
 }
 

@@ -13,6 +13,12 @@
 // comply), 128, or 1152 (SigLIP-so400m): 1152 = 4.5 x 256, so the last of
 // its five 256-column steps covers 128 columns and runs on lanes 0..31 —
 // the idle half loads and stores nothing and adds zeros to the sums.
+// 1408 (InternVideo2-1B) = 5.5 x 256 is the same case.
+//
+// RMSNorm (InternVideo2): cc_rmsnorm_bf16 is the same wave-per-row pass
+// without the mean, y = bf16(x * rsqrt(sum x^2 / H + eps)) * w, and
+// cc_qk_rmsnorm_bf16 runs it in place on the q and k sections of a QKV
+// GEMM output, one wave per (row, section).
 //
 // Also here: the row statistics of the folded LayerNorm.
 // cc_ln_stats_bf16 reads x once and writes f32 partial sums (sum, sum of
@@ -103,6 +109,71 @@ __global__ void k_layernorm_bf16(const __bf16* __restrict__ x,
       o[j] = (__bf16)((vals[c + j] - mean) * rstd * wv[j] + bv[j]);
     *(bf16x4*)(yr + i0) = o;
   }
+}
+
+// One row of RMSNorm, y = bf16(x * rstd) * w with rstd = rsqrt(sum x^2 / H
+// + eps): the normalised value is rounded to bf16 BEFORE the weight
+// multiply (the order of the InternVideo2 module: normalise in f32, cast to
+// the input type, multiply by the weight).  xr == yr is allowed: a lane
+// stores only the columns it loaded, after the last load of the row.
+template <int CHUNK>
+__device__ __forceinline__ void rms_row(const __bf16* xr,
+                                        const float* __restrict__ w,
+                                        __bf16* yr, int H, float eps,
+                                        int lane) {
+  float vals[(CHUNK + 3) / 4 * 4];
+  float ss = 0.0f;
+#pragma unroll
+  for (int c = 0; c < CHUNK; c += 4) {
+    bf16x4 p = {};
+    if (step_live<CHUNK>(c, lane)) p = *(const bf16x4*)(xr + c * 64 + 4 * lane);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      vals[c + j] = (float)p[j];
+      ss += vals[c + j] * vals[c + j];
+    }
+  }
+  ss = wave_sum(ss);
+  const float rstd = rsqrtf(ss * (1.0f / (float)H) + eps);
+#pragma unroll
+  for (int c = 0; c < CHUNK; c += 4) {
+    if (!step_live<CHUNK>(c, lane)) continue;
+    const int i0 = c * 64 + 4 * lane;
+    f32x4 wv = *(const f32x4*)(w + i0);
+    bf16x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      o[j] = (__bf16)((float)(__bf16)(vals[c + j] * rstd) * wv[j]);
+    *(bf16x4*)(yr + i0) = o;
+  }
+}
+
+template <int CHUNK>
+__global__ void k_rmsnorm_bf16(const __bf16* __restrict__ x,
+                               const float* __restrict__ w,
+                               __bf16* __restrict__ y, long M, int H,
+                               float eps) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;          // 4 waves per block
+  const long row = (long)blockIdx.x * 4 + wave;
+  if (row >= M) return;
+  rms_row<CHUNK>(x + row * H, w, y + row * H, H, eps, lane);
+}
+
+// QK-norm in place on qkv [M, ld]: wave u normalises section u & 1 (0: q,
+// columns [0, H) with wq; 1: k, columns [H, 2H) with wk) of row u >> 1.
+// Columns from 2H on are never addressed.
+template <int CHUNK>
+__global__ void k_qk_rmsnorm_bf16(__bf16* qkv, const float* __restrict__ wq,
+                                  const float* __restrict__ wk, long M, int H,
+                                  long ld, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const long unit = (long)blockIdx.x * 4 + wave;
+  if (unit >= 2 * M) return;
+  const int sec = (int)(unit & 1);
+  __bf16* xr = qkv + (unit >> 1) * ld + (long)sec * H;
+  rms_row<CHUNK>(xr, sec ? wk : wq, xr, H, eps, lane);
 }
 
 // out[row] = LN( src(row) + pos[t] ) where row = f*tokens + t,
@@ -268,13 +339,33 @@ __global__ void k_ln_finalize(const float2* __restrict__ stats,
   }
 }
 
+// The RMSNorm form of k_ln_finalize: murstd[r] = (0, rsqrt(sumsq/H + eps)),
+// the pair with which the LN_IN epilogue rstd * (acc - mean * s) + c is
+// RMSNorm.  Same lanes, same order of additions; the sums are not read.
+__global__ void k_rms_finalize(const float2* __restrict__ stats,
+                               float2* __restrict__ murstd, long M, int P,
+                               long row_step, float inv_n, float eps) {
+  const long row = ((long)blockIdx.x * 256 + threadIdx.x) >> 3;
+  const int j = threadIdx.x & 7;
+  float ss = 0.0f;
+  if (row < M) {
+    const float2* sr = stats + row * row_step * P;
+    for (int p = j; p < P; p += 8) ss += sr[p].y;
+  }
+  ss = group_sum<8>(ss);
+  if (row < M && j == 0)
+    murstd[row] = make_float2(0.0f, rsqrtf(ss * inv_n + eps));
+}
+
 // the CHUNK (= H / 64) values the templates are instantiated for; the
 // entry points reject every other H before they launch, so the switches
 // below need no default.  CC_LN_CHUNKS256: whole 256-column steps, all
-// three templates; CC_LN_CHUNKS adds 18 (H = 1152) for k_layernorm_bf16
-// and k_ln_stats_bf16, which handle the partial last step.
+// three templates; CC_LN_CHUNKS adds 18 (H = 1152) and 22 (H = 1408) for
+// k_layernorm_bf16, k_ln_stats_bf16 and the RMSNorm kernels, which handle
+// the partial last step (the RMSNorm kernels take H = 128 as CHUNK 2 the
+// same way: one step, lanes 0..31).
 #define CC_LN_CHUNKS256(X) X(4) X(8) X(12) X(16) X(32) X(48) X(64)
-#define CC_LN_CHUNKS(X) CC_LN_CHUNKS256(X) X(18)
+#define CC_LN_CHUNKS(X) CC_LN_CHUNKS256(X) X(18) X(22)
 
 #define OR_EQ(C) || H == 64 * C
 bool has_chunk(int64_t H) { return false CC_LN_CHUNKS(OR_EQ); }
@@ -326,6 +417,79 @@ extern "C" int cc_ln_finalize(const void* stats, int64_t M, int64_t H,
   });
 }
 
+extern "C" int cc_rms_finalize(const void* stats, int64_t M, int64_t H,
+                               int64_t row_step, float eps, void* murstd,
+                               uint64_t stream) {
+  if (!stats || !murstd || M <= 0 || H <= 0 || row_step <= 0)
+    return cc::set_error(CC_ERR_INVALID, "bad rms_finalize args");
+  if (!cc::ln_h_supported(H))
+    return cc::set_error(CC_ERR_UNSUPPORTED, "unsupported H %lld", (long long)H);
+  dim3 block(256), grid((M + 31) / 32);  // 8 lanes per row
+  return cc::timed_launch("ln_finalize", stream, [&] {
+    hipLaunchKernelGGL(k_rms_finalize, grid, block, 0, (hipStream_t)stream,
+                       (const float2*)stats, (float2*)murstd, (long)M,
+                       (int)(H / 64), (long)row_step, 1.0f / (float)H, eps);
+  });
+}
+
+extern "C" int cc_rmsnorm_bf16(const void* x, const void* w, void* y,
+                               int64_t M, int64_t H, float eps,
+                               uint64_t stream) {
+  if (!x || !w || !y || M <= 0 || H <= 0)
+    return cc::set_error(CC_ERR_INVALID, "bad rmsnorm args");
+  if (!cc::ln_h_supported(H))
+    return cc::set_error(CC_ERR_UNSUPPORTED,
+                         "rmsnorm: H must be a width cc_layernorm_bf16 "
+                         "takes (got %lld)",
+                         (long long)H);
+  dim3 block(256), grid((M + 3) / 4);
+  return cc::timed_launch("rmsnorm_bf16", stream, [&] {
+    switch (H / 64) {
+#define CASE(C)                                                            \
+  case C:                                                                  \
+    hipLaunchKernelGGL(k_rmsnorm_bf16<C>, grid, block, 0,                  \
+                       (hipStream_t)stream, (const __bf16*)x,              \
+                       (const float*)w, (__bf16*)y, (long)M, (int)H, eps); \
+    break;
+      CASE(2)
+      CC_LN_CHUNKS(CASE)
+#undef CASE
+    }
+  });
+}
+
+extern "C" int cc_qk_rmsnorm_bf16(void* qkv, int64_t M, int64_t H, int64_t ld,
+                                  const void* wq, const void* wk, float eps,
+                                  uint64_t stream) {
+  if (!qkv || !wq || !wk || M <= 0 || H <= 0)
+    return cc::set_error(CC_ERR_INVALID, "bad qk_rmsnorm args");
+  if (ld < 2 * H || ld % 4 != 0)
+    return cc::set_error(CC_ERR_INVALID,
+                         "qk_rmsnorm: ld %lld must hold the q and k sections "
+                         "(>= 2H = %lld) and keep rows 8-byte aligned "
+                         "(ld %% 4 == 0)",
+                         (long long)ld, (long long)(2 * H));
+  if (!cc::ln_h_supported(H))
+    return cc::set_error(CC_ERR_UNSUPPORTED,
+                         "qk_rmsnorm: H must be a width cc_layernorm_bf16 "
+                         "takes (got %lld)",
+                         (long long)H);
+  dim3 block(256), grid((2 * M + 3) / 4);  // one wave per (row, section)
+  return cc::timed_launch("qk_rmsnorm", stream, [&] {
+    switch (H / 64) {
+#define CASE(C)                                                            \
+  case C:                                                                  \
+    hipLaunchKernelGGL(k_qk_rmsnorm_bf16<C>, grid, block, 0,               \
+                       (hipStream_t)stream, (__bf16*)qkv, (const float*)wq, \
+                       (const float*)wk, (long)M, (int)H, (long)ld, eps);  \
+    break;
+      CASE(2)
+      CC_LN_CHUNKS(CASE)
+#undef CASE
+    }
+  });
+}
+
 extern "C" int cc_layernorm_bf16(const void* x, const void* w, const void* b,
                                  void* y, int64_t M, int64_t H, float eps,
                                  uint64_t stream) {
@@ -333,8 +497,8 @@ extern "C" int cc_layernorm_bf16(const void* x, const void* w, const void* b,
     return cc::set_error(CC_ERR_INVALID, "bad layernorm args");
   if (!cc::ln_h_supported(H))
     return cc::set_error(CC_ERR_UNSUPPORTED,
-                         "H must be 128, 1152 or an instantiated k*256, "
-                         "<=4096 (got %lld)",
+                         "H must be 128, 1152, 1408 or an instantiated "
+                         "k*256, <=4096 (got %lld)",
                          (long long)H);
   dim3 block(256), grid((M + 3) / 4);
   return cc::timed_launch("layernorm_bf16", stream, [&] {

@@ -167,6 +167,14 @@ def _declare(lib: ctypes.CDLL) -> None:
         c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p,
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64,
         c.c_int, c.c_float, c.c_uint64]
+    lib.cc_rms_finalize.argtypes = lib.cc_ln_finalize.argtypes
+    lib.cc_gemm_bf16_rms.argtypes = lib.cc_gemm_bf16_ln.argtypes
+    lib.cc_rmsnorm_bf16.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_float,
+        c.c_uint64]
+    lib.cc_qk_rmsnorm_bf16.argtypes = [
+        c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p,
+        c.c_float, c.c_uint64]
     lib.cc_embed_assemble_ln.argtypes = [
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
         c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_float, c.c_uint64]

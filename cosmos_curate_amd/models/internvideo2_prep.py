@@ -1,9 +1,9 @@
 """InternVideo2 / Cosmos-Embed1 input-frame preparation (MI355X route).
 
-The IV2/CE1 model WEIGHTS are unavailable offline, so their end-model
-numerics stay parity-unpinned this round (SURVEY.md §2 row "Embedding
-models" / §8c); what the rebuild ships — per that row's contract — is the
-exact PREPROCESSING math their stages feed the networks with:
+The exact PREPROCESSING math the InternVideo2 / Cosmos-Embed1 stages feed
+their networks with.  The InternVideo2 tower that consumes it is
+models/internvideo2_vit.py (through models/internvideo2.py); Cosmos-Embed1
+has no tower here.
 
 - ``formulate_input_frames`` mirrors internvideo2_mm.py:391-438
   ``_construct_frames``: temporal subsample step = len//fnum then [:fnum],

@@ -44,7 +44,7 @@ from cosmos_curate_amd import hotpath
 from cosmos_curate_amd.models import clip_weights as cw
 
 # VitConfig.act -> cc_gemm_bf16_ex epilogue activation code
-ACT_CODES = {"quick_gelu": 1, "gelu_tanh": 2}
+ACT_CODES = {"quick_gelu": 1, "gelu_tanh": 2, "gelu_erf": 3}
 
 
 def cc_linear(
@@ -117,6 +117,20 @@ def fold_layernorm(
     return w_fold.contiguous(), colsum.contiguous(), cbias.contiguous()
 
 
+def fold_rmsnorm(
+    w: torch.Tensor, b: torch.Tensor | None, weight: torch.Tensor
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fold_layernorm for an RMSNorm (weight only, no mean subtraction):
+    linear(rmsnorm(x), w, b) = rstd * (W' x) + c with W' = bf16(w * weight)
+    per input column and c = b, or zeros for a layer without bias.  The
+    column sum multiplies a zero mean in the epilogue and is not needed:
+    zeros.  Returns (W' bf16, zeros f32, c f32) for cc_linear_rms."""
+    w_fold = (w.float() * weight.float()[None, :]).to(torch.bfloat16)
+    zeros = torch.zeros(w.shape[0], dtype=torch.float32)
+    cbias = zeros.clone() if b is None else b.float()
+    return w_fold.contiguous(), zeros, cbias.contiguous()
+
+
 def cc_ln_stats(x: torch.Tensor) -> torch.Tensor:
     """Row statistics of x [M, H] bf16 as the folded GEMMs read them: f32
     partial (sum, sum of squares) per 64-column block, [M, H/64, 2]."""
@@ -139,11 +153,13 @@ def cc_linear_ln(
     act: int,
     eps: float,
     row_step: int = 1,
+    rms: bool = False,
 ) -> torch.Tensor:
     """act(linear(layer_norm(x))) with the LayerNorm folded away
     (cc_gemm_bf16_ln): x is the raw LN input, ``stats`` its row statistics,
     (w_fold, colsum, cbias) from fold_layernorm.  ``row_step`` > 1 takes
-    every row_step-th row of x and of stats, in place."""
+    every row_step-th row of x and of stats, in place.  ``rms``: the norm is
+    an RMSNorm (cc_gemm_bf16_rms; see cc_linear_rms)."""
     lib = hotpath.require_gpu()
     assert x.dtype == torch.bfloat16 and x.is_contiguous()
     assert w_fold.dtype == torch.bfloat16 and w_fold.is_contiguous()
@@ -154,14 +170,65 @@ def cc_linear_ln(
     out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
     murstd = torch.empty((M, 2), dtype=torch.float32, device=x.device)
     stream = torch.cuda.current_stream(x.device).cuda_stream
+    entry = lib.cc_gemm_bf16_rms if rms else lib.cc_gemm_bf16_ln
     hotpath.check(
-        lib.cc_gemm_bf16_ln(
+        entry(
             x.data_ptr(), row_step, stats.data_ptr(), murstd.data_ptr(),
             w_fold.data_ptr(), colsum.data_ptr(), cbias.data_ptr(),
             out.data_ptr(), M, N, K, act, eps, stream,
         )
     )
     return out
+
+
+def cc_linear_rms(
+    x: torch.Tensor,
+    stats: torch.Tensor,
+    w_fold: torch.Tensor,
+    zeros: torch.Tensor,
+    cbias: torch.Tensor,
+    act: int,
+    eps: float,
+) -> torch.Tensor:
+    """act(linear(rmsnorm(x))) with the RMSNorm folded away
+    (cc_gemm_bf16_rms): x is the raw input, ``stats`` its row statistics (the
+    same partials cc_linear_ln reads), (w_fold, zeros, cbias) from
+    fold_rmsnorm."""
+    return cc_linear_ln(x, stats, w_fold, zeros, cbias, act, eps, rms=True)
+
+
+def cc_rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
+    """RMSNorm over the last dim of a bf16 GPU tensor, f32 weight
+    (cc_rmsnorm_bf16): bf16(bf16(x * rstd) * w)."""
+    lib = hotpath.require_gpu()
+    assert x.dtype == torch.bfloat16
+    xc = x.contiguous()
+    out = torch.empty_like(xc)
+    h = xc.shape[-1]
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    hotpath.check(
+        lib.cc_rmsnorm_bf16(
+            xc.data_ptr(), w.data_ptr(), out.data_ptr(), xc.numel() // h, h,
+            eps, stream))
+    return out
+
+
+def cc_qk_rmsnorm(
+    qkv: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, eps: float
+) -> torch.Tensor:
+    """QK-normalisation in place on a fused-QKV GEMM output [M, 3H] bf16
+    (cc_qk_rmsnorm_bf16): the q and the k section of every row each go
+    through an RMSNorm of width H; v is not touched.  Returns qkv."""
+    lib = hotpath.require_gpu()
+    assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous()
+    M, ld = qkv.shape
+    H = ld // 3
+    stream = torch.cuda.current_stream(qkv.device).cuda_stream
+    hotpath.check(
+        lib.cc_qk_rmsnorm_bf16(
+            qkv.data_ptr(), M, H, ld, wq.data_ptr(), wk.data_ptr(), eps,
+            stream))
+    return qkv
 
 
 def cc_linear_res_stats(

@@ -8,7 +8,8 @@ clip payloads + per-clip metadata + embeddings parquet + summary.json):
 
     <output>/clips/<uuid>.bin              clip payload (mp4 or raw-NV12)
     <output>/metas/v0/<uuid>.json          span, source, errors
-    <output>/clip_embd/chunk_<i>.parquet   id + embedding (pyarrow)
+    <output>/clip_embd/chunk_<i>.parquet   id + embedding (pyarrow);
+                                           iv2_embd/ under internvideo2
     <output>/summary.json                  counts + clips/sec + stage perf
 
 The output tree names follow the reference's helpers (:167-223:
@@ -30,6 +31,22 @@ from cosmos_curate_amd.core.interfaces.stage_interface import (
 )
 from cosmos_curate_amd.core.utils.performance_utils import StageTimer, summarize_perf_stats
 from cosmos_curate_amd.pipelines.video.utils.data_model import SplitPipeTask
+
+
+def embd_stem(embedding_algorithm: str) -> str:
+    """Directory of the embeddings parquet (metadata_writer_stage.py:226-235
+    ``_embd_stem``): ``iv2_embd`` for InternVideo2, ``<algorithm>_embd``
+    otherwise."""
+    if embedding_algorithm == "internvideo2":
+        return "iv2_embd"
+    return f"{embedding_algorithm}_embd"
+
+
+def clip_embedding_of(clip, embedding_algorithm: str):
+    """The embedding the run's algorithm produced on this clip, or None."""
+    if embedding_algorithm == "internvideo2":
+        return clip.intern_video_2_embedding
+    return clip.clip_embedding
 
 
 class ClipWriterStage(CuratorStage):
@@ -65,7 +82,7 @@ class ClipWriterStage(CuratorStage):
     def stage_setup(self) -> None:
         (self._output_path / "clips").mkdir(parents=True, exist_ok=True)
         (self._output_path / "metas" / "v0").mkdir(parents=True, exist_ok=True)
-        (self._output_path / f"{self._embedding_algorithm}_embd").mkdir(
+        (self._output_path / embd_stem(self._embedding_algorithm)).mkdir(
             parents=True, exist_ok=True
         )
 
@@ -83,7 +100,7 @@ class ClipWriterStage(CuratorStage):
         )
         dest = (
             self._output_path
-            / f"{self._embedding_algorithm}_embd"
+            / embd_stem(self._embedding_algorithm)
             / f"chunk_{self._rank}_{self._chunk_counter:06d}.parquet"
         )
         pq.write_table(table, dest)
@@ -102,6 +119,7 @@ class ClipWriterStage(CuratorStage):
                         # don't collide (AV writer camera_id convention)
                         cid = (f"cam{cam_idx}_{clip.uuid}" if multicam
                                else str(clip.uuid))
+                        emb = clip_embedding_of(clip, self._embedding_algorithm)
                         if self._upload_clips and clip.encoded_data:
                             payload = clip.encoded_data.resolve()
                             with open(self._output_path / "clips" / f"{cid}.bin",
@@ -119,13 +137,13 @@ class ClipWriterStage(CuratorStage):
                             "span": list(clip.span),
                             "duration": clip.duration,
                             "errors": clip.errors,
-                            "has_embedding": clip.clip_embedding is not None,
+                            "has_embedding": emb is not None,
                         }
                         (self._output_path / "metas" / "v0" / f"{cid}.json").write_text(
                             json.dumps(meta, indent=1)
                         )
-                        if clip.clip_embedding is not None:
-                            emb_rows.append((cid, clip.clip_embedding))
+                        if emb is not None:
+                            emb_rows.append((cid, emb))
                             video.clip_stats.num_with_embeddings += 1
                         if clip.errors:
                             video.clip_stats.num_with_errors += 1
@@ -152,7 +170,7 @@ def write_split_summary(
     num_clips = sum(len(v.clips) for t in output_tasks for v in t.videos)
     num_with_embeddings = sum(
         1 for t in output_tasks for v in t.videos for c in v.clips
-        if c.clip_embedding is not None
+        if clip_embedding_of(c, embedding_algorithm) is not None
     )
     num_with_errors = sum(
         1 for t in output_tasks for v in t.videos for c in v.clips if c.errors

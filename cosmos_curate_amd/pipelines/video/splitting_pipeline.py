@@ -15,6 +15,9 @@ Stage order (reference _assemble_stages):
     ClipFrameExtractionStage        (GPU decode->sample->resize)
     ClipFrameCreationStage
     ClipEmbeddingStage              (--embedding-model tower, MFMA path)
+      or, under --embedding-algorithm internvideo2:
+    InternVideo2FrameCreationStage
+    InternVideo2EmbeddingStage      (video tower, MFMA path)
     ClipWriterStage
 """
 
@@ -211,7 +214,17 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
             score_only=args.motion_filter == "score-only",
             log_stats=True,
         ))
-    if args.generate_embeddings:
+    iv2 = args.embedding_algorithm == "internvideo2"
+    if args.generate_embeddings and iv2:
+        from cosmos_curate_amd.pipelines.video.embedding.internvideo2_stages import (
+            InternVideo2EmbeddingStage,
+            InternVideo2FrameCreationStage,
+        )
+
+        stages.append(InternVideo2FrameCreationStage(
+            target_fps=args.target_clip_fps, log_stats=True))
+        stages.append(InternVideo2EmbeddingStage(log_stats=True))
+    elif args.generate_embeddings:
         res = args.clip_extraction_target_res
         stages.append(ClipFrameCreationStage(
             target_fps=args.target_clip_fps,
@@ -220,7 +233,9 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
         ))
         stages.append(ClipEmbeddingStage(
             log_stats=True, variant=args.embedding_model))
-    stages.append(ClipWriterStage(args.output_clip_path, log_stats=True))
+    stages.append(ClipWriterStage(
+        args.output_clip_path, log_stats=True,
+        **({"embedding_algorithm": "internvideo2"} if iv2 else {})))
     return stages
 
 
@@ -245,12 +260,17 @@ def _setup_parser(parser: argparse.ArgumentParser) -> None:
     parser.add_argument("--generate-embeddings", action="store_true", default=True)
     parser.add_argument("--no-embeddings", "--no-generate-embeddings",
                         dest="generate_embeddings", action="store_false")
-    parser.add_argument("--embedding-algorithm", default="clip")
+    parser.add_argument("--embedding-algorithm", default="clip",
+                        help="internvideo2 embeds each clip with the "
+                        "InternVideo2 video tower (512 wide, written under "
+                        "iv2_embd/); any other value names the run and "
+                        "embeds with the --embedding-model image tower")
     parser.add_argument("--embedding-model", default="vit_b32",
                         choices=sorted(EMBEDDING_MODELS),
                         help="vision tower of the embedding stage "
                         "(clip_weights.CONFIGS); frames are resized on device "
-                        "to the tower's input size where they differ")
+                        "to the tower's input size where they differ; "
+                        "ignored under --embedding-algorithm internvideo2")
     parser.add_argument("--aesthetic-threshold", type=float, default=None)
     parser.add_argument("--clip-extraction-target-res", type=int, default=224,
                         help="square target resolution for extracted frames; "

@@ -93,6 +93,10 @@ class Clip:
     # embedding produced by the configured embedder (CLIP/SigLIP)
     clip_embedding: npt.NDArray[np.float32] | None = None
     clip_embedding_frames: LazyData = dataclasses.field(default_factory=LazyData)
+    # InternVideo2 (data_model.py:226-229): model input frames (a LazyData
+    # over a (1, T, 3, H, W) f32 device tensor) and the video embedding
+    intern_video_2_frames: LazyData | None = None
+    intern_video_2_embedding: npt.NDArray[np.float32] | None = None
     # aesthetic filter (data_model.py:241)
     aesthetic_score: float | None = None
     # motion filter (data_model.py:236-239)

@@ -307,9 +307,13 @@ int cc_gemm_bf16(const void* A, const void* B, void* C,
                  int64_t M, int64_t N, int64_t K,
                  const float* bias, int c_dtype, uint64_t stream);
 /* Fused-epilogue form: act 0 = none, 1 = quick-gelu (x*sigmoid(1.702x),
- * the CLIP MLP activation); residual (bf16 [M,N], may be NULL) is added
- * after the activation — fuses the MLP/attention elementwise kernels into
- * the producing GEMM. */
+ * the CLIP MLP activation), 2 = tanh-gelu (SigLIP), 3 = erf-gelu
+ * (0.5x(1 + erf(x/sqrt 2)), torch gelu approximate="none"; InternVideo2);
+ * residual (bf16 [M,N], may be NULL) is added after the activation — fuses
+ * the MLP/attention elementwise kernels into the producing GEMM (DESIGN.md
+ * §3).  No other act value is taken: CC_ERR_INVALID, in every entry with
+ * an act argument.  act 3 is instantiated with a bias and without a
+ * residual (an fc1); any other act-3 call returns CC_ERR_UNSUPPORTED. */
 int cc_gemm_bf16_ex(const void* A, const void* B, void* C,
                     int64_t M, int64_t N, int64_t K,
                     const float* bias, int c_dtype, int act,
@@ -407,10 +411,28 @@ int cc_attn_cls(const void* q, const void* k, const void* v, int64_t ldkv,
                 float scale, uint64_t stream);
 
 /* ---- fused bf16 LayerNorm (replaces torch layer_norm in the ViT
- * forward; f32 stats/affine; H = 128, 1152 or one of the instantiated
- * multiples of 256: 256, 512, 768, 1024, 2048, 3072, 4096). */
+ * forward; f32 stats/affine; H = 128, 1152, 1408 or one of the
+ * instantiated multiples of 256: 256, 512, 768, 1024, 2048, 3072, 4096). */
 int cc_layernorm_bf16(const void* x, const void* w, const void* b, void* y,
                       int64_t M, int64_t H, float eps, uint64_t stream);
+
+/* ---- bf16 RMSNorm (InternVideo2), H as for
+ * cc_layernorm_bf16, w f32 [H]:
+ *   y = bf16( bf16(x * rsqrt(sum x^2 / H + eps)) * w )
+ * f32 statistics; the normalised value is rounded to bf16 before the weight
+ * multiply, the order of the model's own module.  Timed as "rmsnorm_bf16".
+ * cc_qk_rmsnorm_bf16: the same, in place, on the q and k sections of a QKV
+ * GEMM output qkv [M, ld] bf16: columns [0, H) of every row with wq,
+ * columns [H, 2H) with wk, each section a norm of width H of its own;
+ * columns from 2H on are not touched.  ld = row stride in elements, >= 2H,
+ * ld % 4 == 0; one wave per (row, section).  Timed as "qk_rmsnorm".
+ * Both: CC_ERR_INVALID on null pointers, non-positive sizes or a bad ld,
+ * CC_ERR_UNSUPPORTED on another width, before any launch. */
+int cc_rmsnorm_bf16(const void* x, const void* w, void* y, int64_t M,
+                    int64_t H, float eps, uint64_t stream);
+int cc_qk_rmsnorm_bf16(void* qkv, int64_t M, int64_t H, int64_t ld,
+                       const void* wq, const void* wk, float eps,
+                       uint64_t stream);
 
 /* ---- LayerNorm folded into the GEMM that consumes it.
  * With W' = W * gamma (per column k, rounded to bf16), s[n] = sum_k W'[n,k]
@@ -437,6 +459,13 @@ int cc_layernorm_bf16(const void* x, const void* w, const void* b, void* y,
  * [frames*seq, K] tensor in place, on the 128-tile body).  murstd is
  * [M, 2] f32 scratch the call fills (cc_ln_finalize) and reads.  Timed as
  * "gemm_bf16" plus "ln_finalize".
+ * cc_rms_finalize / cc_gemm_bf16_rms: the RMSNorm forms.  RMSNorm is the
+ * same expression with mean = 0 and rstd = rsqrt(sum x^2/H + eps), so
+ * cc_rms_finalize writes murstd[r] = (0, rstd) from the same partials and
+ * cc_gemm_bf16_rms is cc_gemm_bf16_ln running that finalize: with
+ * Wfold = bf16(W * w_rms) per column and cbias = b (zeros for a layer
+ * without bias), C = act(linear(rmsnorm(x))).  colsum is multiplied by the
+ * zero mean; pass zeros.
  * All: CC_ERR_INVALID on null pointers or non-positive sizes,
  * CC_ERR_UNSUPPORTED on a width without LayerNorm kernels, before any
  * launch. */
@@ -451,6 +480,12 @@ int cc_gemm_bf16_ln(const void* A, int64_t row_step, const void* stats,
                     void* murstd, const void* Wfold, const float* colsum,
                     const float* cbias, void* C, int64_t M, int64_t N,
                     int64_t K, int act, float eps, uint64_t stream);
+int cc_rms_finalize(const void* stats, int64_t M, int64_t H, int64_t row_step,
+                    float eps, void* murstd, uint64_t stream);
+int cc_gemm_bf16_rms(const void* A, int64_t row_step, const void* stats,
+                     void* murstd, const void* Wfold, const float* colsum,
+                     const float* cbias, void* C, int64_t M, int64_t N,
+                     int64_t K, int act, float eps, uint64_t stream);
 
 /* ---- fused ViT embedding assembly: out[f*tokens + t] =
  * LayerNorm( (t==0 ? cls : tok[f*(tokens-1)+t-1]) + pos[t] ).
