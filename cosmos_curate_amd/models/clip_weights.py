@@ -37,6 +37,8 @@ class VitConfig:
     has_cls: bool = True       # SigLIP towers have no class token
     act: str = "quick_gelu"    # "quick_gelu" (CLIP) | "gelu_tanh" (SigLIP)
     ln_eps: float = 1e-5       # layer_norm_eps: CLIP 1e-5, SigLIP 1e-6
+    norm: str = "layernorm"    # encoder-layer norm: "layernorm" | "rmsnorm"
+    qk_norm: bool = False      # RMSNorm on q and on k before attention
 
     @property
     def num_pos(self) -> int:

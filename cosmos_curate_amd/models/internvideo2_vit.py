@@ -18,18 +18,20 @@ tokens; 16 heads, output projection to 768), ``vision_proj`` to 512 and an
 L2 norm.  The CLIP-teacher decoders of the model's forward do not feed the
 embedding and are not evaluated.
 
-Everything that is O(tokens) runs on the hand-written kernels, through the
-primitives of vit_encoder:
+Everything that is O(tokens) runs on the hand-written kernels (DESIGN.md
+§17).  The patch weight, the blocks and the _linear / _ln primitives are
+the shared encoder (vit_encoder.VitEncoderAMD): its layer run with the
+config's RMSNorm, QK-norm and erf-GELU and a QKV without bias, over the
+checkpoint's ``vision_encoder.blocks.{i}.*`` keys (_layer_weights).  On the
+folded route that is one cc_ln_stats pass over the assembled sequence and,
+per block, QKV GEMM with rmsnorm1 folded in, QK-norm in place on its
+output, cc_attn at head dim 88, out-proj + residual + statistics, fc1 with
+rmsnorm2 folded in and the erf-GELU epilogue, fc2 + residual + statistics.
+This file keeps what is InternVideo2's own:
 
-- the patch GEMM, conv bias in its epilogue;
-- one cc_ln_stats pass over the assembled sequence; after that the GEMMs
-  that write the residual stream hand the row statistics on;
-- per block: QKV GEMM with rmsnorm1 folded in (cc_linear_rms), QK-norm in
-  place on its output (cc_qk_rmsnorm), cc_attn at head dim 88, out-proj +
-  residual + statistics, fc1 with rmsnorm2 folded in and the erf-GELU
-  epilogue, fc2 + residual + statistics;
-- LayerScale is folded into the out-proj and fc2 weights and biases once at
-  construction (row n scaled by gamma[n] in f32, then cast to bf16): exact
+- the patch bias, the CLS token and the position table;
+- LayerScale, folded into the out-proj and fc2 weights and biases as they
+  are gathered (row n scaled by gamma[n] in f32, then cast to bf16): exact
   in real arithmetic, free at run time, and the reason the residual
   epilogue stays usable;
 - the pooling head's K and V are one [2*hidden, hidden] GEMM with
@@ -40,8 +42,9 @@ What is O(clips) runs in torch f32, following the SigLIP MAP head's
 precedent: the token mean, LayerNorm_q, the q projection, the one-query
 softmax over K/V, the projection to 768, vision_proj and the L2 norm.
 
-``fold_norms = False`` runs cc_rmsnorm / cc_layernorm plus the plain GEMMs
-instead, for A/B runs and parity tests.
+``fold_ln = False`` runs cc_rmsnorm / cc_layernorm plus the plain GEMMs
+instead, for A/B runs and parity tests; it is also the route of CPU tensors
+(the structure tests, with _linear monkeypatched to torch).
 
 Out of scope, and refused loudly: T = 1 (the single-image position table),
 a position table of another T than the config's (no temporal
@@ -55,18 +58,9 @@ import torch
 
 from cosmos_curate_amd.models import internvideo2_weights as iw
 from cosmos_curate_amd.models.vit_encoder import (
-    ACT_CODES,
     VitEncoderAMD,
-    cc_linear,
     cc_linear_ln,
-    cc_linear_res_stats,
-    cc_linear_rms,
-    cc_ln_stats,
-    cc_layernorm,
-    cc_qk_rmsnorm,
-    cc_rmsnorm,
     fold_layernorm,
-    fold_rmsnorm,
     patchify,
 )
 
@@ -83,31 +77,17 @@ def fold_layerscale(
 
 class InternVideo2VisionTowerAMD(VitEncoderAMD):
     """(B, T, 3, image, image) pixels or prebuilt patch rows -> (B, proj)
-    f32 unit-norm video embeddings.
-
-    Shares VitEncoderAMD's attention call and input contract; the weights
-    (checkpoint key names, internvideo2_weights) and the block are its own.
-    """
-
-    fold_norms = True
+    f32 unit-norm video embeddings."""
 
     def __init__(
         self,
         sd: dict[str, torch.Tensor],
         cfg: iw.InternVideo2Config = iw.INTERNVIDEO2_1B,
-        layers: int | None = None,
     ) -> None:
-        """``layers``: build only the first so many blocks (tests)."""
-        torch.nn.Module.__init__(self)
         if cfg.num_frames < 2:
             msg = ("InternVideo2 tower: num_frames 1 needs the single-image "
                    "position table, which is not implemented")
             raise NotImplementedError(msg)
-        self.cfg = cfg
-        self.heads = cfg.heads
-        self.layers = cfg.layers if layers is None else layers
-        self.scale = float(cfg.hidden // cfg.heads) ** -0.5
-        self.act = ACT_CODES["gelu_erf"]
         ve = "vision_encoder."
         H = cfg.hidden
         pos = sd[ve + "pos_embed"]
@@ -120,50 +100,19 @@ class InternVideo2VisionTowerAMD(VitEncoderAMD):
                    "interpolation of a position table is not implemented: "
                    "set num_frames to the checkpoint's")
             raise ValueError(msg)
+        super().__init__(sd, cfg, ve)
         reg = self.register_buffer
-        to_bf = lambda t: t.to(torch.bfloat16).contiguous()  # noqa: E731
         to_f32 = lambda t: t.float().contiguous()  # noqa: E731
-
-        k0 = 3 * cfg.patch * cfg.patch
-        self.patch_k = (k0 + 63) // 64 * 64  # cc_gemm needs K % 64 == 0
-        # [H, 3, 1, P, P]: tubelet 1, so the 3-D conv is a per-frame GEMM
-        w_patch = sd[ve + "patch_embed.proj.weight"].reshape(H, k0)
-        reg("w_patch", to_bf(torch.nn.functional.pad(w_patch, (0, self.patch_k - k0))))
         reg("b_patch", to_f32(sd[ve + "patch_embed.proj.bias"]))
         reg("cls_token", to_f32(sd[ve + "cls_token"].reshape(1, 1, H)))
         reg("pos_embed", to_f32(pos))
-        for i in range(self.layers):
-            b = f"{ve}blocks.{i}."
-            if b + "attn.qkv.bias" in sd or b + "attn.q_bias" in sd:
-                msg = "InternVideo2 tower: a qkv bias is not implemented"
-                raise NotImplementedError(msg)
-            reg(f"norm1_w_{i}", to_f32(sd[b + "norm1.weight"]))
-            reg(f"norm2_w_{i}", to_f32(sd[b + "norm2.weight"]))
-            reg(f"qn_w_{i}", to_f32(sd[b + "attn.q_norm.weight"]))
-            reg(f"kn_w_{i}", to_f32(sd[b + "attn.k_norm.weight"]))
-            reg(f"w_qkv_{i}", to_bf(sd[b + "attn.qkv.weight"]))
-            reg(f"w_fc1_{i}", to_bf(sd[b + "mlp.fc1.weight"]))
-            reg(f"b_fc1_{i}", to_f32(sd[b + "mlp.fc1.bias"]))
-            # LayerScale folded into the GEMM that feeds the residual add
-            for name, lin, ls in (("out", "attn.proj", "ls1"), ("fc2", "mlp.fc2", "ls2")):
-                w, bias = fold_layerscale(
-                    sd[b + lin + ".weight"], sd[b + lin + ".bias"], sd[b + ls + ".gamma"])
-                reg(f"w_{name}_{i}", w)
-                reg(f"b_{name}_{i}", bias)
-            # rmsnorm1 / rmsnorm2 folded into QKV / fc1 (derived buffers)
-            for name, w, bias, nw in (
-                ("qkv", sd[b + "attn.qkv.weight"], None, f"norm1_w_{i}"),
-                ("fc1", sd[b + "mlp.fc1.weight"], sd[b + "mlp.fc1.bias"], f"norm2_w_{i}"),
-            ):
-                for pre, t in zip(("wf", "s", "c"),
-                                  fold_rmsnorm(w, bias, getattr(self, nw))):
-                    reg(f"{pre}_{name}_{i}", t, persistent=False)
         # pooling head: K and V as one GEMM, their LayerNorms folded in
         cp = ve + "clip_projector."
         for n in "kv":
             reg(f"pool_ln{n}_w", to_f32(sd[cp + f"norm1_{n}.weight"]))
             reg(f"pool_ln{n}_b", to_f32(sd[cp + f"norm1_{n}.bias"]))
-            reg(f"pool_w{n}", to_bf(sd[cp + f"cross_attn.{n}.weight"]))
+            reg(f"pool_w{n}",
+                sd[cp + f"cross_attn.{n}.weight"].to(torch.bfloat16).contiguous())
             reg(f"pool_b{n}", to_f32(sd[cp + f"cross_attn.{n}_bias"]))
         folded = [
             fold_layernorm(sd[cp + f"cross_attn.{n}.weight"],
@@ -184,31 +133,32 @@ class InternVideo2VisionTowerAMD(VitEncoderAMD):
         reg("vproj_w", to_f32(sd["vision_proj.weight"]))
         reg("vproj_b", to_f32(sd["vision_proj.bias"]))
 
-    def _block_folded(
-        self, h: torch.Tensor, stats: torch.Tensor, i: int, n: int, seq: int
-    ) -> tuple[torch.Tensor, torch.Tensor]:
-        """Block ``i`` without norm kernels: (h (n*seq, H), its row
-        statistics) -> the same pair for the block's output."""
-        p = self._layer_params(i)
-        eps = self.cfg.rms_eps
-        qkv = cc_linear_rms(h, stats, p("wf_qkv"), p("s_qkv"), p("c_qkv"), 0, eps)
-        cc_qk_rmsnorm(qkv, p("qn_w"), p("kn_w"), eps)
-        attn = self._attention(qkv, n, seq)
-        h, stats = cc_linear_res_stats(attn, p("w_out"), p("b_out"), h)
-        y = cc_linear_rms(h, stats, p("wf_fc1"), p("s_fc1"), p("c_fc1"), self.act, eps)
-        return cc_linear_res_stats(y, p("w_fc2"), p("b_fc2"), h)
+    def _patch_weight(self, sd: dict[str, torch.Tensor]) -> torch.Tensor:
+        # [H, 3, 1, P, P]: tubelet 1, so the 3-D conv is a per-frame GEMM
+        return sd[self.prefix + "patch_embed.proj.weight"]
 
-    def _block(self, h: torch.Tensor, i: int, n: int, seq: int) -> torch.Tensor:
-        """Block ``i`` with the stand-alone norm kernel and plain GEMMs."""
-        p = self._layer_params(i)
-        eps = self.cfg.rms_eps
-        qkv = cc_linear(cc_rmsnorm(h, p("norm1_w"), eps), p("w_qkv"), None)
-        cc_qk_rmsnorm(qkv, p("qn_w"), p("kn_w"), eps)
-        attn = self._attention(qkv, n, seq)
-        h = cc_linear(attn, p("w_out"), p("b_out"), residual=h)
-        y = cc_linear(cc_rmsnorm(h, p("norm2_w"), eps), p("w_fc1"), p("b_fc1"),
-                      act=self.act)
-        return cc_linear(y, p("w_fc2"), p("b_fc2"), residual=h)
+    def _layer_weights(
+        self, sd: dict[str, torch.Tensor], i: int
+    ) -> dict[str, torch.Tensor | None]:
+        b = f"{self.prefix}blocks.{i}."
+        if b + "attn.qkv.bias" in sd or b + "attn.q_bias" in sd:
+            msg = "InternVideo2 tower: a qkv bias is not implemented"
+            raise NotImplementedError(msg)
+        # LayerScale folded into the GEMM that feeds the residual add
+        w_out, b_out = fold_layerscale(
+            sd[b + "attn.proj.weight"], sd[b + "attn.proj.bias"], sd[b + "ls1.gamma"])
+        w_fc2, b_fc2 = fold_layerscale(
+            sd[b + "mlp.fc2.weight"], sd[b + "mlp.fc2.bias"], sd[b + "ls2.gamma"])
+        return {
+            "w_qkv": sd[b + "attn.qkv.weight"], "b_qkv": None,
+            "w_out": w_out, "b_out": b_out,
+            "ln1_w": sd[b + "norm1.weight"], "ln1_b": None,
+            "ln2_w": sd[b + "norm2.weight"], "ln2_b": None,
+            "w_fc1": sd[b + "mlp.fc1.weight"], "b_fc1": sd[b + "mlp.fc1.bias"],
+            "w_fc2": w_fc2, "b_fc2": b_fc2,
+            "qn_w": sd[b + "attn.q_norm.weight"],
+            "kn_w": sd[b + "attn.k_norm.weight"],
+        }
 
     def _pool(self, h: torch.Tensor, stats: torch.Tensor | None, n: int,
               seq: int) -> torch.Tensor:
@@ -221,9 +171,9 @@ class InternVideo2VisionTowerAMD(VitEncoderAMD):
                               self.c_pool_kv, 0, cfg.pool_ln_eps)
         else:
             kv = torch.cat([
-                cc_linear(cc_layernorm(h, getattr(self, f"pool_ln{x}_w"),
-                                       getattr(self, f"pool_ln{x}_b"), cfg.pool_ln_eps),
-                          getattr(self, f"pool_w{x}"), getattr(self, f"pool_b{x}"))
+                self._linear(self._ln(h, getattr(self, f"pool_ln{x}_w"),
+                                      getattr(self, f"pool_ln{x}_b"), cfg.pool_ln_eps),
+                             getattr(self, f"pool_w{x}"), getattr(self, f"pool_b{x}"))
                 for x in "kv"], dim=1)
         kv = kv.reshape(n, seq, 2, cfg.pool_heads, hd).float()
         k = kv[:, :, 0].transpose(1, 2)  # (n, heads, seq, hd)
@@ -262,17 +212,15 @@ class InternVideo2VisionTowerAMD(VitEncoderAMD):
             assert n is not None
             assert patches.shape == (n * T * cfg.tokens_per_frame, self.patch_k)
         seq = cfg.num_pos
-        tok = cc_linear(patches, self.w_patch, self.b_patch)
+        tok = self._linear(patches, self.w_patch, self.b_patch)
         h = torch.cat([self.cls_token.to(torch.bfloat16).expand(n, 1, H),
                        tok.reshape(n, seq - 1, H)], dim=1)
-        h = (h.float() + self.pos_embed).to(torch.bfloat16).reshape(n * seq, H)
-        if self.fold_norms:
-            stats = cc_ln_stats(h)
-            for i in range(self.layers):
-                h, stats = self._block_folded(h, stats, i, n, seq)
+        h = (h.float() + self.pos_embed).to(torch.bfloat16)
+        stats = None
+        if self._folds(h):
+            # the last fc2's statistics feed the pooling head's K/V GEMM
+            h, stats = self._encode_folded(h, n, seq, self.layers)
         else:
-            stats = None
-            for i in range(self.layers):
-                h = self._block(h, i, n, seq)
-        e = self._pool(h, stats, n, seq)
+            h = self._encode(h, n, seq)
+        e = self._pool(h.reshape(n * seq, H), stats, n, seq)
         return e / torch.linalg.vector_norm(e, dim=-1, keepdim=True)

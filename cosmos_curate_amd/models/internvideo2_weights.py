@@ -46,6 +46,15 @@ class InternVideo2Config:
     pool_heads: int = 16       # attn_pool_num_heads
     rms_eps: float = 1e-6
     pool_ln_eps: float = 1e-5
+    # what the shared encoder layer (vit_encoder) reads besides the geometry
+    act: str = "gelu_erf"
+    norm: str = "rmsnorm"
+    qk_norm: bool = True
+
+    @property
+    def ln_eps(self) -> float:
+        """The block-norm eps under the name the shared encoder reads."""
+        return self.rms_eps
 
     @property
     def tokens_per_frame(self) -> int:

@@ -1,12 +1,16 @@
-"""The ViT encoder both vision towers share, MI355X-native.
+"""The ViT encoder the three vision towers share, MI355X-native.
 
-Everything CLIP (clip_vit.ClipVisionTowerAMD) and SigLIP
-(siglip_vit.SiglipVisionTowerAMD) have in common: the patch-embed-as-GEMM
-front, the fused-QKV weight layout and the pre-norm encoder layer
-[LN1, QKV GEMM, attention, out-proj + residual, LN2, fc1 + activation,
-fc2 + residual].  What differs between the towers is data, read from
-clip_weights.VitConfig (activation, LN eps, geometry) and the state-dict
-key prefix; embeddings and pooling stay in the tower files.
+Everything CLIP (clip_vit.ClipVisionTowerAMD), SigLIP
+(siglip_vit.SiglipVisionTowerAMD) and InternVideo2
+(internvideo2_vit.InternVideo2VisionTowerAMD) have in common: the
+patch-embed-as-GEMM front, the fused-QKV weight layout and the pre-norm
+encoder layer [norm1, QKV GEMM, (QK-norm,) attention, out-proj + residual,
+norm2, fc1 + activation, fc2 + residual].  What differs between the towers
+is data: the config (clip_weights.VitConfig or a config with its fields:
+geometry, activation, norm kind and eps, QK-norm) and where the checkpoint
+keeps a layer's tensors (_layer_weights: which keys, and whether QKV has a
+bias).  The layer branches on those values, never on the tower it serves;
+embeddings and pooling stay in the tower files.
 
 - every contraction runs on the hand-written MFMA bf16 kernel
   (cc_gemm_bf16*, csrc/cc_gemm.hip) through the C ABI, bias / activation /
@@ -17,12 +21,13 @@ key prefix; embeddings and pooling stay in the tower files.
   multiples of 8 from 64 to 128, asked of cc_attn_plan itself; any other
   head dim takes torch sdpa (``force_sdpa = True`` sends every tower
   there, for A/B runs);
-- LN1 and LN2 never materialise on the GPU: their affine part is folded
-  into the QKV / fc1 weights once at construction (fold_layernorm) and the
-  GEMM epilogue finishes the normalisation from per-row statistics that
-  the GEMM producing the residual stream wrote (DESIGN.md §14;
-  ``fold_ln = False`` restores the LN kernel + plain GEMM chain);
-- the remaining layernorms run the fused HIP kernel (f32 statistics);
+- norm1 and norm2 never materialise on the GPU: their affine part is folded
+  into the QKV / fc1 weights once at construction (fold_layernorm, or
+  fold_rmsnorm for an RMSNorm tower) and the GEMM epilogue finishes the
+  normalisation from per-row statistics that the GEMM producing the
+  residual stream wrote (``fold_ln = False`` restores
+  the norm kernel + plain GEMM chain);
+- the remaining norms run the fused HIP kernels (f32 statistics);
 - an MLP width that is no multiple of 64 (SigLIP-so400m's 4304) is
   zero-padded once at construction to the next one, which the GEMM's
   K % 64 == 0 needs — exact, see VitEncoderAMD;
@@ -124,7 +129,7 @@ def fold_rmsnorm(
     linear(rmsnorm(x), w, b) = rstd * (W' x) + c with W' = bf16(w * weight)
     per input column and c = b, or zeros for a layer without bias.  The
     column sum multiplies a zero mean in the epilogue and is not needed:
-    zeros.  Returns (W' bf16, zeros f32, c f32) for cc_linear_rms."""
+    zeros.  Returns (W' bf16, zeros f32, c f32) for cc_linear_ln(rms=True)."""
     w_fold = (w.float() * weight.float()[None, :]).to(torch.bfloat16)
     zeros = torch.zeros(w.shape[0], dtype=torch.float32)
     cbias = zeros.clone() if b is None else b.float()
@@ -159,7 +164,8 @@ def cc_linear_ln(
     (cc_gemm_bf16_ln): x is the raw LN input, ``stats`` its row statistics,
     (w_fold, colsum, cbias) from fold_layernorm.  ``row_step`` > 1 takes
     every row_step-th row of x and of stats, in place.  ``rms``: the norm is
-    an RMSNorm (cc_gemm_bf16_rms; see cc_linear_rms)."""
+    an RMSNorm (cc_gemm_bf16_rms) and (w_fold, colsum, cbias) come from
+    fold_rmsnorm; the statistics are the same partials."""
     lib = hotpath.require_gpu()
     assert x.dtype == torch.bfloat16 and x.is_contiguous()
     assert w_fold.dtype == torch.bfloat16 and w_fold.is_contiguous()
@@ -181,27 +187,17 @@ def cc_linear_ln(
     return out
 
 
-def cc_linear_rms(
-    x: torch.Tensor,
-    stats: torch.Tensor,
-    w_fold: torch.Tensor,
-    zeros: torch.Tensor,
-    cbias: torch.Tensor,
-    act: int,
-    eps: float,
-) -> torch.Tensor:
-    """act(linear(rmsnorm(x))) with the RMSNorm folded away
-    (cc_gemm_bf16_rms): x is the raw input, ``stats`` its row statistics (the
-    same partials cc_linear_ln reads), (w_fold, zeros, cbias) from
-    fold_rmsnorm."""
-    return cc_linear_ln(x, stats, w_fold, zeros, cbias, act, eps, rms=True)
-
-
 def cc_rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
-    """RMSNorm over the last dim of a bf16 GPU tensor, f32 weight
+    """RMSNorm over the last dim of a bf16 tensor, f32 weight
     (cc_rmsnorm_bf16): bf16(bf16(x * rstd) * w)."""
-    lib = hotpath.require_gpu()
     assert x.dtype == torch.bfloat16
+    if not x.is_cuda:
+        # CPU tensors only (the monkeypatched structure tests): the
+        # kernel's rounding order in torch f32
+        xf = x.float()
+        y = xf * torch.rsqrt(xf.pow(2).mean(dim=-1, keepdim=True) + eps)
+        return (y.to(torch.bfloat16).float() * w).to(torch.bfloat16)
+    lib = hotpath.require_gpu()
     xc = x.contiguous()
     out = torch.empty_like(xc)
     h = xc.shape[-1]
@@ -219,10 +215,14 @@ def cc_qk_rmsnorm(
     """QK-normalisation in place on a fused-QKV GEMM output [M, 3H] bf16
     (cc_qk_rmsnorm_bf16): the q and the k section of every row each go
     through an RMSNorm of width H; v is not touched.  Returns qkv."""
-    lib = hotpath.require_gpu()
     assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous()
     M, ld = qkv.shape
     H = ld // 3
+    if not qkv.is_cuda:  # CPU tensors only, as in cc_rmsnorm
+        qkv[:, :H] = cc_rmsnorm(qkv[:, :H], wq, eps)
+        qkv[:, H:2 * H] = cc_rmsnorm(qkv[:, H:2 * H], wk, eps)
+        return qkv
+    lib = hotpath.require_gpu()
     stream = torch.cuda.current_stream(qkv.device).cuda_stream
     hotpath.check(
         lib.cc_qk_rmsnorm_bf16(
@@ -317,13 +317,19 @@ class VitEncoderAMD(torch.nn.Module):
     """Patch-embed weight + ``cfg.layers`` pre-norm encoder layers.
 
     ``prefix`` is what the state dict puts before ``embeddings.`` /
-    ``encoder.layers.``.  The patch-embed GEMM's K = 3*patch^2 is
-    zero-padded to the kernel's 64-multiple requirement (588 -> 640 for
-    L/14) — exact, the padded columns multiply zeros.
+    ``encoder.layers.`` in the HF key layout; a tower whose checkpoint is
+    laid out otherwise overrides _patch_weight / _layer_weights.  The
+    patch-embed GEMM's K = 3*patch^2 is zero-padded to the kernel's
+    64-multiple requirement (588 -> 640 for L/14) — exact, the padded
+    columns multiply zeros.
 
-    ``fold_ln`` (default True): on the GPU, LN1 and LN2 are folded into the
-    QKV and fc1 GEMMs (_layer_folded).  False runs the LN kernel and the
-    plain GEMMs — for A/B runs and parity tests; it is also what CPU
+    ``cfg.norm`` makes norm1 / norm2 LayerNorms or RMSNorms (eps
+    ``cfg.ln_eps`` either way); with ``cfg.qk_norm`` q and k each go through
+    an RMSNorm of the hidden width, at the same eps, before attention.
+
+    ``fold_ln`` (default True): on the GPU, norm1 and norm2 are folded into
+    the QKV and fc1 GEMMs (_layer_folded).  False runs the norm kernel and
+    the plain GEMMs — for A/B runs and parity tests; it is also what CPU
     tensors and head dims cc_attn does not take get.
 
     ``force_sdpa`` (default False): True sends attention through torch
@@ -350,9 +356,9 @@ class VitEncoderAMD(torch.nn.Module):
         self.layers = cfg.layers
         self.scale = 1.0 / math.sqrt(cfg.hidden // cfg.heads)
         self.act = ACT_CODES[cfg.act]
+        self.rms = {"layernorm": False, "rmsnorm": True}[cfg.norm]
+        self.prefix = prefix
         reg = self.register_buffer
-        to_bf = lambda t: t.to(torch.bfloat16).contiguous()  # noqa: E731
-        to_f32 = lambda t: t.float().contiguous()  # noqa: E731
 
         k0 = 3 * cfg.patch * cfg.patch
         self.patch_k = (k0 + 63) // 64 * 64  # cc_gemm needs K % 64 == 0
@@ -361,40 +367,63 @@ class VitEncoderAMD(torch.nn.Module):
         mlp_pad = self.intermediate - cfg.intermediate
         pad_rows = lambda t: torch.nn.functional.pad(  # noqa: E731
             t, (0, 0, 0, mlp_pad) if t.dim() == 2 else (0, mlp_pad))
-        w_patch = sd[prefix + "embeddings.patch_embedding.weight"].reshape(
-            cfg.hidden, k0)
+        w_patch = self._patch_weight(sd).reshape(cfg.hidden, k0)
         if self.patch_k != k0:
             w_patch = torch.nn.functional.pad(w_patch, (0, self.patch_k - k0))
-        reg("w_patch", to_bf(w_patch))
+        reg("w_patch", w_patch.to(torch.bfloat16).contiguous())
         for i in range(cfg.layers):
-            q = f"{prefix}encoder.layers.{i}."
-            # fused QKV: [3*hidden, hidden] rows ordered (q, k, v)
-            qkv = [q + f"self_attn.{x}_proj." for x in "qkv"]
-            reg(f"w_qkv_{i}", to_bf(torch.cat([sd[x + "weight"] for x in qkv], dim=0)))
-            reg(f"b_qkv_{i}", to_f32(torch.cat([sd[x + "bias"] for x in qkv])))
-            reg(f"w_out_{i}", to_bf(sd[q + "self_attn.out_proj.weight"]))
-            reg(f"b_out_{i}", to_f32(sd[q + "self_attn.out_proj.bias"]))
-            reg(f"ln1_w_{i}", to_f32(sd[q + "layer_norm1.weight"]))
-            reg(f"ln1_b_{i}", to_f32(sd[q + "layer_norm1.bias"]))
-            reg(f"ln2_w_{i}", to_f32(sd[q + "layer_norm2.weight"]))
-            reg(f"ln2_b_{i}", to_f32(sd[q + "layer_norm2.bias"]))
-            reg(f"w_fc1_{i}", to_bf(pad_rows(sd[q + "mlp.fc1.weight"])))
-            reg(f"b_fc1_{i}", to_f32(pad_rows(sd[q + "mlp.fc1.bias"])))
-            reg(f"w_fc2_{i}", to_bf(torch.nn.functional.pad(
-                sd[q + "mlp.fc2.weight"], (0, mlp_pad))))
-            reg(f"b_fc2_{i}", to_f32(sd[q + "mlp.fc2.bias"]))
-            # LN1 / LN2 folded into the GEMM they feed (derived, so kept
+            t = self._layer_weights(sd, i)
+            assert (t["ln1_b"] is None) == (t["ln2_b"] is None) == self.rms
+            t["w_fc1"], t["b_fc1"] = pad_rows(t["w_fc1"]), pad_rows(t["b_fc1"])
+            t["w_fc2"] = torch.nn.functional.pad(t["w_fc2"], (0, mlp_pad))
+            # GEMM weights (w_*) bf16, everything else f32; an absent bias
+            # is a None buffer
+            for name, v in t.items():
+                if v is not None:
+                    dt = torch.bfloat16 if name.startswith("w_") else torch.float32
+                    v = v.to(dt).contiguous()
+                reg(f"{name}_{i}", v)
+            # norm1 / norm2 folded into the GEMM they feed (derived, so kept
             # out of the state dict); row order (q, k, v) as in w_qkv
-            for name, w, b, ln in (
-                ("qkv", torch.cat([sd[x + "weight"] for x in qkv], dim=0),
-                 getattr(self, f"b_qkv_{i}"), "ln1"),
-                ("fc1", pad_rows(sd[q + "mlp.fc1.weight"]),
-                 getattr(self, f"b_fc1_{i}"), "ln2"),
-            ):
-                folded = fold_layernorm(
-                    w, b, getattr(self, f"{ln}_w_{i}"), getattr(self, f"{ln}_b_{i}"))
-                for pre, t in zip(("wf", "s", "c"), folded):
-                    reg(f"{pre}_{name}_{i}", t, persistent=False)
+            p = self._layer_params(i)
+            for name, ln in (("qkv", "ln1"), ("fc1", "ln2")):
+                w, b = t["w_" + name], p("b_" + name)
+                folded = (
+                    fold_rmsnorm(w, b, p(ln + "_w")) if self.rms
+                    else fold_layernorm(w, b, p(ln + "_w"), p(ln + "_b")))
+                for pre, f in zip(("wf", "s", "c"), folded):
+                    reg(f"{pre}_{name}_{i}", f, persistent=False)
+
+    def _patch_weight(self, sd: dict[str, torch.Tensor]) -> torch.Tensor:
+        """The patch-embedding weight; flattens to [hidden, 3*patch^2]."""
+        return sd[self.prefix + "embeddings.patch_embedding.weight"]
+
+    def _layer_weights(
+        self, sd: dict[str, torch.Tensor], i: int
+    ) -> dict[str, torch.Tensor | None]:
+        """Layer ``i``'s checkpoint tensors, unconverted and unpadded, under
+        the buffer base names, in registration order: ``w_qkv`` [3*hidden,
+        hidden] with rows ordered (q, k, v) and ``b_qkv`` (None: QKV has no
+        bias), ``w_out`` / ``b_out``, ``ln1_w`` / ``ln1_b`` and ``ln2_w`` /
+        ``ln2_b`` (the biases None for an RMSNorm), ``w_fc1`` / ``b_fc1``,
+        ``w_fc2`` / ``b_fc2``, and with ``cfg.qk_norm`` ``qn_w`` / ``kn_w``.
+        Here: the HF key layout under ``prefix``."""
+        q = f"{self.prefix}encoder.layers.{i}."
+        qkv = [q + f"self_attn.{x}_proj." for x in "qkv"]
+        return {
+            "w_qkv": torch.cat([sd[x + "weight"] for x in qkv], dim=0),
+            "b_qkv": torch.cat([sd[x + "bias"] for x in qkv]),
+            "w_out": sd[q + "self_attn.out_proj.weight"],
+            "b_out": sd[q + "self_attn.out_proj.bias"],
+            "ln1_w": sd[q + "layer_norm1.weight"],
+            "ln1_b": sd[q + "layer_norm1.bias"],
+            "ln2_w": sd[q + "layer_norm2.weight"],
+            "ln2_b": sd[q + "layer_norm2.bias"],
+            "w_fc1": sd[q + "mlp.fc1.weight"],
+            "b_fc1": sd[q + "mlp.fc1.bias"],
+            "w_fc2": sd[q + "mlp.fc2.weight"],
+            "b_fc2": sd[q + "mlp.fc2.bias"],
+        }
 
     # the one contraction primitive; tests may monkeypatch this
     def _linear(
@@ -407,8 +436,15 @@ class VitEncoderAMD(torch.nn.Module):
     ) -> torch.Tensor:
         return cc_linear(x, w, b, act, residual)
 
-    def _ln(self, x: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-        return cc_layernorm(x, w, b, self.cfg.ln_eps)
+    # the one stand-alone norm primitive; no bias makes it an RMSNorm
+    def _ln(
+        self, x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None,
+        eps: float | None = None,
+    ) -> torch.Tensor:
+        eps = self.cfg.ln_eps if eps is None else eps
+        if b is None:
+            return cc_rmsnorm(x, w, eps)
+        return cc_layernorm(x, w, b, eps)
 
     def _layer_params(self, i: int):
         """Accessor of layer ``i``'s buffers by base name (``"w_qkv"``...)."""
@@ -471,6 +507,8 @@ class VitEncoderAMD(torch.nn.Module):
         p = self._layer_params(i)
         y = self._ln(h, p("ln1_w"), p("ln1_b"))
         qkv_flat = self._linear(y.reshape(n * seq, H), p("w_qkv"), p("b_qkv"))
+        if self.cfg.qk_norm:
+            cc_qk_rmsnorm(qkv_flat, p("qn_w"), p("kn_w"), self.cfg.ln_eps)
         attn = self._attention(qkv_flat, n, seq)
         # residual add fused into the out-proj epilogue
         h = self._linear(
@@ -485,24 +523,27 @@ class VitEncoderAMD(torch.nn.Module):
         ).reshape(n, seq, H)
 
     def _folds(self, h: torch.Tensor) -> bool:
-        """Whether ``h`` takes the folded-LayerNorm route."""
+        """Whether ``h`` takes the folded-norm route."""
         return self.fold_ln and self._native_attn(h)
 
     def _layer_folded(
         self, h: torch.Tensor, stats: torch.Tensor, i: int, n: int, seq: int
     ) -> tuple[torch.Tensor, torch.Tensor]:
-        """Encoder layer ``i`` without LN kernels: (h (n*seq, H), its row
+        """Encoder layer ``i`` without norm kernels: (h (n*seq, H), its row
         statistics) -> the same pair for the layer's output.  QKV and fc1
         read the raw residual stream and normalise in their epilogue;
         out-proj and fc2 write the statistics of what they store."""
         p = self._layer_params(i)
         eps = self.cfg.ln_eps
         qkv_flat = cc_linear_ln(
-            h, stats, p("wf_qkv"), p("s_qkv"), p("c_qkv"), 0, eps)
+            h, stats, p("wf_qkv"), p("s_qkv"), p("c_qkv"), 0, eps, rms=self.rms)
+        if self.cfg.qk_norm:
+            cc_qk_rmsnorm(qkv_flat, p("qn_w"), p("kn_w"), eps)
         attn = self._attention(qkv_flat, n, seq)
         h, stats = cc_linear_res_stats(attn, p("w_out"), p("b_out"), h)
         y = cc_linear_ln(
-            h, stats, p("wf_fc1"), p("s_fc1"), p("c_fc1"), self.act, eps)
+            h, stats, p("wf_fc1"), p("s_fc1"), p("c_fc1"), self.act, eps,
+            rms=self.rms)
         return cc_linear_res_stats(y, p("w_fc2"), p("b_fc2"), h)
 
     def _encode_folded(

@@ -67,7 +67,7 @@ def _run(geometry, stress=False):
     tower = _tower(sd, cfg)
     folded = tower(px).cpu()
     again = tower(px).cpu()
-    tower.fold_norms = False
+    tower.fold_ln = False
     unfolded = tower(px).cpu()
     return want, folded, again, unfolded
 

@@ -6,13 +6,19 @@ reference's own arithmetic (transformers CLIPVisionModelWithProjection,
 models/clip.py:64-74) by monkeypatching the one contraction primitive
 (_linear) to torch on CPU.  The MFMA kernel itself is pinned on the GPU in
 tests/test_gpu_vit.py; this test makes a GPU failure attributable to the
-kernel alone.
+kernel alone.  The SigLIP and the InternVideo2 tower (the latter against
+tests/iv2_ref.py) are pinned the same way.
 """
+
+import dataclasses
+import functools
 
 import numpy as np
 import pytest
 import torch
 
+import iv2_ref
+from cosmos_curate_amd.models import internvideo2_weights as iw
 from cosmos_curate_amd.models.clip_vit import ClipVisionTowerAMD
 from cosmos_curate_amd.models.clip_weights import make_clip_vit_b32_weights
 from oracle import vit as oracle_vit
@@ -30,6 +36,8 @@ def _torch_linear(self, x, w, b, act=0, residual=None):
         y = y * torch.sigmoid(1.702 * y)
     if act == 2:
         y = torch.nn.functional.gelu(y, approximate="tanh")
+    if act == 3:
+        y = torch.nn.functional.gelu(y, approximate="none")
     if residual is not None:
         y = y + residual.float()
     return y.to(torch.bfloat16)
@@ -181,3 +189,90 @@ def test_siglip_config_geometry():
     assert cfg.num_pos == 256  # no CLS token
     assert cfg.hidden // cfg.heads == 64  # attn_mid head-dim contract
     assert (3 * cfg.patch * cfg.patch) % 64 == 0
+
+
+# ---- InternVideo2 on the shared layer: RMSNorm, QK-norm, no QKV bias -----
+
+def _iv2_case(case):
+    """(cfg, weights): the tiny geometry, or the real widths at 2 blocks,
+    T = 2, image 56 (33 tokens), plain or with outlier channels."""
+    if case == "tiny":
+        from test_iv2_cpu import TINY
+
+        return TINY, iw.make_internvideo2_weights(TINY)
+    cfg = dataclasses.replace(iw.INTERNVIDEO2_1B, layers=2, num_frames=2, image=56)
+    make = (iw.make_internvideo2_weights_stress if case == "real_stress"
+            else iw.make_internvideo2_weights)
+    return cfg, make(cfg)
+
+
+@functools.lru_cache(maxsize=None)
+def _iv2_run(case):
+    """(cfg, fp32 reference, the tower on CPU with _linear patched to torch,
+    its _linear calls), once per case.  Two clips that share their first
+    frame, as in tests/test_gpu_iv2_tower.py."""
+    from cosmos_curate_amd.models.internvideo2_vit import InternVideo2VisionTowerAMD
+
+    cfg, sd = _iv2_case(case)
+    g = torch.Generator().manual_seed(1000 * cfg.num_frames + cfg.image)
+    px = torch.randn(2, cfg.num_frames, 3, cfg.image, cfg.image, generator=g)
+    px[1, 0] = px[0, 0]
+    px = px.to(torch.bfloat16).float()
+    want = iv2_ref.InternVideo2Ref(sd, cfg)(px)
+    calls = []
+
+    def counting(self, x, w, b, act=0, residual=None):
+        calls.append((x.shape[0], b is not None, act, residual is not None))
+        return _torch_linear(self, x, w, b, act, residual)
+
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(InternVideo2VisionTowerAMD, "_linear", counting)
+        got = InternVideo2VisionTowerAMD(sd, cfg)(px)
+    return cfg, want, got, calls
+
+
+def _cos(a, b):
+    return torch.nn.functional.cosine_similarity(a.double(), b.double(), dim=-1)
+
+
+@pytest.mark.parametrize("case", ["tiny", "real", "real_stress"])
+def test_iv2_tower_matches_fp32_reference(case):
+    """InternVideo2VisionTowerAMD's arithmetic (patch bias, CLS + position
+    add, the shared layer with RMSNorm / QK-norm / erf-GELU and the folded
+    LayerScale, the pooling head) vs tests/iv2_ref.py in fp32 on the same
+    state dict.  The bound is BASELINE.json's tower cosine."""
+    cfg, want, got, _ = _iv2_run(case)
+    assert got.shape == want.shape == (2, cfg.proj) and got.dtype == torch.float32
+    torch.testing.assert_close(
+        torch.linalg.vector_norm(got, dim=-1), torch.ones(2), rtol=0, atol=1e-5)
+    cos = _cos(got, want)
+    print(f"{case}: per-clip cosine vs fp32 reference {cos.tolist()}")
+    assert cos.min() >= 0.999, cos
+
+
+def test_iv2_tower_linear_calls():
+    """The shared layer loop as InternVideo2 drives it: the patch GEMM with
+    its bias, 4 GEMMs per block on all n*seq rows — QKV without a bias, the
+    erf-GELU code on fc1 and nowhere else — and the pooling head's K and V."""
+    cfg, _, _, calls = _iv2_run("tiny")
+    rows = 2 * cfg.num_pos
+    block = [(rows, False, 0, False), (rows, True, 0, True),   # qkv, out+res
+             (rows, True, 3, False), (rows, True, 0, True)]    # fc1, fc2+res
+    assert len(calls) == 4 * cfg.layers + 3
+    assert calls == ([(rows - 2, True, 0, False)] + block * cfg.layers
+                     + [(rows, True, 0, False)] * 2)
+
+
+@pytest.mark.parametrize("case", ["tiny", "real"])
+def test_iv2_tower_reads_every_frame(case):
+    """The two clips share their first frame.  A tower that ignored time
+    would pass the parity check with one embedding for both
+    (test_gpu_iv2_tower.test_tower_reads_every_frame, on the CPU route)."""
+    _, want, got, _ = _iv2_run(case)
+    ref_between = float(_cos(want[0], want[1]))
+    got_between = float(_cos(got[0], got[1]))
+    print(f"{case}: cosine between the clips, fp32 {ref_between:.6f}, "
+          f"tower {got_between:.6f}")
+    assert ref_between < 0.999, "the reference cannot tell the clips apart"
+    assert not torch.equal(got[0], got[1])
+    assert got_between < 0.9999

@@ -8,7 +8,7 @@ ops in bf16, the legs alternating in one process.
 Per number of frames T (4 = 1025 tokens per clip, 8 = 2049) the legs are,
 eager, on the same pixels:
   - native, norms folded (InternVideo2VisionTowerAMD),
-  - native with fold_norms = False (cc_rmsnorm / cc_layernorm + plain GEMMs),
+  - native with fold_ln = False (cc_rmsnorm / cc_layernorm + plain GEMMs),
   - torch bf16: tests/iv2_ref.py's module moved to the device in bf16 — the
     yardstick.
 Per-forward device time from HIP events around each forward; median, min,
@@ -86,12 +86,12 @@ def bench(sd_max: dict, cfg_max, T: int, clips: int, warmup: int,
 
     def native(fold: bool):
         def fn() -> torch.Tensor:
-            tower.fold_norms = fold
+            tower.fold_ln = fold
             return tower(px)
         return fn
 
     legs = {"native, norms folded": native(True),
-            "native, fold_norms=False": native(False),
+            "native, fold_ln=False": native(False),
             "torch bf16 (yardstick)": lambda: ref(px)}
     outs = {k: fn().float() for k, fn in legs.items()}
     torch.cuda.synchronize()
@@ -102,7 +102,7 @@ def bench(sd_max: dict, cfg_max, T: int, clips: int, warmup: int,
     lines = [f"tower: {cfg.name}, {cfg.layers} blocks, eager, {clips} clips x T = {T} "
              f"({cfg.num_pos} tokens per clip); per-clip cosine with the yardstick, "
              f"min: folded {cos['native, norms folded']:.6f}, unfolded "
-             f"{cos['native, fold_norms=False']:.6f}"]
+             f"{cos['native, fold_ln=False']:.6f}"]
     ty = times["torch bf16 (yardstick)"]
     ymed = float(np.median(ty))
     spread = float((np.percentile(ty, 90) - np.percentile(ty, 10)) / ymed)
@@ -118,7 +118,7 @@ def bench(sd_max: dict, cfg_max, T: int, clips: int, warmup: int,
 
     # kernel-time split of a folded forward, from the library's timers
     reps = 3
-    tower.fold_norms = True
+    tower.fold_ln = True
     hotpath.timing_enable(True)
     try:
         for _ in range(reps):
