@@ -19,6 +19,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <type_traits>
@@ -446,6 +447,229 @@ __global__ void k_resize_bicubic_u8(const unsigned char* __restrict__ in,
         v = v + hsum * wy[3];
     }
     o[c] = round_u8(v);
+  }
+}
+
+// ---------------- u8 NHWC antialiased separable resize (+ crop) ----------------
+// Resize(antialias=True) + CenterCrop of torchvision, computing only the
+// cropped region.  The filter lives in the two per-axis tables of
+// cc_resize_aa_table_build (int32 first[len], int32 count[len],
+// f32 w[len][taps]); the kernel is the same for every filter.  Per output
+// pixel and channel, in f32, multiply then add (this file is built with
+// -ffp-contract=off), bit-exact vs tests/resize_aa_ref.py:
+//   hrow[y] = sum_k wx[ox][k] * float(src[y][firstx[ox] + k])   k ascending from 0.0f
+//   v       = sum_k wy[oy][k] * hrow[firsty[oy] + k]            k ascending from 0.0f
+//   out     = u8(rintf(min(max(v, 0), 255)))
+// rintf is round-half-to-even, which is torch.round in torchvision's
+// _cast_squeeze_out; deliberately NOT this file's round_u8 (half up).
+//
+// One workgroup per (frame, band of kAaBR output rows, block of kAaBC output
+// columns).  hrow[y] depends only on (y, ox, c), so it is computed once per
+// source row and shared by the band's output rows through LDS.  The band's
+// source rows are walked in ascending chunks of as many rows as the LDS
+// holds; each chunk is (0) copied to LDS in 16-byte pieces, (1)
+// reduced horizontally into f32 hrow values in LDS, (2) added into the
+// per-thread vertical accumulators.  Chunks ascend, so every accumulator
+// still sees its terms k ascending: a band that needs several chunks gives
+// the bits of one that needs one, and there is no tap count past which
+// another kernel would be needed.  No atomics, no scratch.
+//
+// The tables are device memory the launcher cannot read, so the kernel does
+// not trust them: first and count are clamped to the source and to `taps`
+// where they are read, and a block whose columns span more source pixels
+// than the LDS holds shortens the spans.  A table that
+// cc_resize_aa_table_build wrote is never changed by either.
+constexpr int kAaBC = 32;          // output columns per workgroup
+constexpr int kAaBR = 8;           // output rows per workgroup
+constexpr int kAaThreads = kAaBC * kAaBR;
+// with s_fx / s_cx 40 KiB per workgroup: 4 workgroups per CU (160 KiB LDS)
+constexpr int kAaLdsBytes = 40960 - 2 * kAaBC * 4;
+constexpr int kAaRowPad = 63;      // most a staged row takes past its span
+// 16 bytes at a 4-byte-aligned address
+struct __attribute__((packed, aligned(4))) aa_quad {
+  unsigned d[4];
+};
+static_assert(CC_RESIZE_AA_MAX_TAPS % 2 == 1, "taps are odd");
+// weights + one staged row of 4096 source pixels + its hrow always fit
+static_assert((kAaBC + kAaBR) * CC_RESIZE_AA_MAX_TAPS * 4 + 4096 * 3 +
+                  kAaRowPad + kAaBC * 12 <= kAaLdsBytes, "LDS budget");
+
+__global__ __launch_bounds__(kAaThreads) void k_resize_aa_u8(
+    const unsigned char* __restrict__ in, int n, int sh, int sw,
+    unsigned char* __restrict__ out, int oh, int ow,
+    const int32_t* __restrict__ ty, int taps_y,
+    const int32_t* __restrict__ tx, int taps_x, int blocks_x, int bands) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kAaLdsBytes];
+  __shared__ int s_fx[kAaBC], s_cx[kAaBC];
+  const int tid = threadIdx.x;
+  const int oxl = tid % kAaBC, oyl = tid / kAaBC;
+  const int bx = blockIdx.x % blocks_x;
+  const int band = (blockIdx.x / blocks_x) % bands;
+  const int f = blockIdx.x / (blocks_x * bands);
+  const int ox0 = bx * kAaBC, oy0 = band * kAaBR;
+  const int ox = ox0 + oxl, oy = oy0 + oyl;
+  const float* __restrict__ wx_g = (const float*)(tx + 2 * (size_t)ow);
+  const float* __restrict__ wy_g = (const float*)(ty + 2 * (size_t)oh);
+
+  // this block's columns, clamped to the source row
+  if (tid < kAaBC) {
+    int fx = 0, cx = 0;
+    if (ox < ow) {
+      fx = min(max(tx[ox], 0), sw);
+      cx = min(max(tx[ow + ox], 0), min(taps_x, sw - fx));
+    }
+    s_fx[tid] = fx;
+    s_cx[tid] = cx;
+  }
+  // this thread's output row, clamped to the source, and the band's rows
+  int fy = 0, cy = 0;
+  int y_lo = sh, y_hi = 0;
+  for (int r = 0; r < kAaBR; r++) {
+    const int o = oy0 + r;
+    if (o >= oh) break;
+    const int a = min(max(ty[o], 0), sh);
+    const int c = min(max(ty[oh + o], 0), min(taps_y, sh - a));
+    if (r == oyl) {
+      fy = a;
+      cy = c;
+    }
+    if (c > 0) {
+      y_lo = min(y_lo, a);
+      y_hi = max(y_hi, a + c);
+    }
+  }
+  __syncthreads();
+  int x_lo = sw, x_hi = 0;
+  for (int i = 0; i < kAaBC; i++)
+    if (s_cx[i] > 0) {
+      x_lo = min(x_lo, s_fx[i]);
+      x_hi = max(x_hi, s_fx[i] + s_cx[i]);
+    }
+  if (x_hi < x_lo) x_lo = x_hi = 0;
+
+  // LDS: wx[kAaBC][taps_x], wy[kAaBR][taps_y], hrow[rc][3][kAaBC] f32, then
+  // rc staged source rows of `stride` bytes
+  float* wxs = (float*)lds;
+  float* wys = wxs + kAaBC * taps_x;
+  float* hrow = wys + kAaBR * taps_y;
+  const int rest = kAaLdsBytes - (kAaBC * taps_x + kAaBR * taps_y) * 4;
+  const int cap_px = (rest - kAaBC * 12 - kAaRowPad) / 3;
+  if (x_hi - x_lo > cap_px) {  // never with a table of the builder's
+    x_hi = x_lo + cap_px;
+    __syncthreads();  // uniform branch: everyone has read s_fx / s_cx
+    if (tid < kAaBC) {
+      const int fx = min(s_fx[tid], x_hi);
+      s_fx[tid] = fx;
+      s_cx[tid] = min(s_cx[tid], x_hi - fx);
+    }
+  }
+  const int span = (x_hi - x_lo) * 3;                  // bytes per row
+  const int stride = ((span + 15) & ~15) + 48;         // multiple of 16
+  const int rc = rest / (stride + kAaBC * 12);         // >= 1
+  unsigned char* srcs = (unsigned char*)(hrow + (size_t)rc * 3 * kAaBC);
+  // 16-byte pieces that cover a row at any alignment; 16*nq <= span + 18
+  const int nq = (span + 18) / 16;
+
+  for (int i = tid; i < kAaBC * taps_x; i += kAaThreads) {
+    const int c = ox0 + i / taps_x;
+    wxs[i] = c < ow ? wx_g[(size_t)c * taps_x + i % taps_x] : 0.0f;
+  }
+  for (int i = tid; i < kAaBR * taps_y; i += kAaThreads) {
+    const int r = oy0 + i / taps_y;
+    wys[i] = r < oh ? wy_g[(size_t)r * taps_y + i % taps_y] : 0.0f;
+  }
+
+  const size_t frame_bytes = (size_t)sh * sw * 3;
+  const unsigned char* in_end = in + (size_t)n * frame_bytes;
+  const unsigned char* frame = in + (size_t)f * frame_bytes;
+  float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f;
+
+  for (int r0 = y_lo; r0 < y_hi; r0 += rc) {
+    const int rows = min(rc, y_hi - r0);
+    __syncthreads();  // the last chunk's readers are done; s_fx, wxs written
+    // (0) rows [r0, r0+rows), bytes [x_lo*3, x_hi*3) -> LDS.  A row starts
+    // at any byte address; it is read as the 16-byte pieces, from the dword
+    // boundary at or below it, that cover it (up to 18 bytes past its span:
+    // the neighbouring pixels, rows or frames) and lands in LDS at the same
+    // offset mod 4.
+    for (int i = tid; i < rows * nq; i += kAaThreads) {
+      const int row = i / nq, q = i - row * nq;
+      const unsigned char* a = frame + ((size_t)(r0 + row) * sw + x_lo) * 3;
+      const unsigned char* p = a - ((size_t)a & 3) + 16 * q;
+      uint4 v;
+      if (p >= in && p + 16 <= in_end) {
+        const aa_quad g = *(const aa_quad*)p;
+        v = make_uint4(g.d[0], g.d[1], g.d[2], g.d[3]);
+      } else {  // the piece straddles the buffer's first or last byte
+        unsigned d[4] = {0, 0, 0, 0};
+        for (int b = 0; b < 16; b++)
+          if (p + b >= in && p + b < in_end)
+            d[b >> 2] |= (unsigned)p[b] << (8 * (b & 3));
+        v = make_uint4(d[0], d[1], d[2], d[3]);
+      }
+      *(uint4*)(srcs + (size_t)row * stride + 16 * q) = v;
+    }
+    __syncthreads();
+    // (1) one thread per (row, column): the three channels' horizontal
+    // sums, four taps (12 bytes = 3 dwords) per step.  Taps past count
+    // take weight 0; the bytes under them are whatever the LDS holds,
+    // always finite as u8, and v + 0*x leaves v's value.
+    for (int i = tid; i < rows * kAaBC; i += kAaThreads) {
+      const int col = i % kAaBC, row = i / kAaBC;
+      const int fx = s_fx[col], cx = s_cx[col];
+      const unsigned char* a = frame + ((size_t)(r0 + row) * sw + x_lo) * 3;
+      // cx > 0 puts fx in [x_lo, x_hi); a column with no taps reads nothing
+      const int b = cx > 0 ? (fx - x_lo) * 3 + (int)((size_t)a & 3) : 0;
+      const unsigned* p = (const unsigned*)(srcs + (size_t)row * stride) + (b >> 2);
+      const unsigned s = b & 3;
+      const float* w = wxs + col * taps_x;
+      float h0 = 0.0f, h1 = 0.0f, h2 = 0.0f;
+      unsigned d0 = p[0];
+      for (int k = 0; k < cx; k += 4) {
+        const unsigned d1 = p[1], d2 = p[2], d3 = p[3];
+        const unsigned e0 = __builtin_amdgcn_alignbyte(d1, d0, s);
+        const unsigned e1 = __builtin_amdgcn_alignbyte(d2, d1, s);
+        const unsigned e2 = __builtin_amdgcn_alignbyte(d3, d2, s);
+        const float w0 = w[k];
+        const float w1 = k + 1 < cx ? w[k + 1] : 0.0f;
+        const float w2 = k + 2 < cx ? w[k + 2] : 0.0f;
+        const float w3 = k + 3 < cx ? w[k + 3] : 0.0f;
+        h0 = h0 + w0 * (float)(e0 & 0xffu);
+        h1 = h1 + w0 * (float)((e0 >> 8) & 0xffu);
+        h2 = h2 + w0 * (float)((e0 >> 16) & 0xffu);
+        h0 = h0 + w1 * (float)(e0 >> 24);
+        h1 = h1 + w1 * (float)(e1 & 0xffu);
+        h2 = h2 + w1 * (float)((e1 >> 8) & 0xffu);
+        h0 = h0 + w2 * (float)((e1 >> 16) & 0xffu);
+        h1 = h1 + w2 * (float)(e1 >> 24);
+        h2 = h2 + w2 * (float)(e2 & 0xffu);
+        h0 = h0 + w3 * (float)((e2 >> 8) & 0xffu);
+        h1 = h1 + w3 * (float)((e2 >> 16) & 0xffu);
+        h2 = h2 + w3 * (float)(e2 >> 24);
+        d0 = d3;
+        p += 3;
+      }
+      float* hr = hrow + (size_t)row * 3 * kAaBC + col;
+      hr[0] = h0;
+      hr[kAaBC] = h1;
+      hr[2 * kAaBC] = h2;
+    }
+    __syncthreads();
+    // (2) this thread's output pixel: the taps whose rows are in the chunk
+    const int k_lo = max(r0 - fy, 0), k_hi = min(cy, r0 + rows - fy);
+    for (int k = k_lo; k < k_hi; k++) {
+      const float w = wys[oyl * taps_y + k];
+      const float* hr = hrow + (size_t)(fy + k - r0) * 3 * kAaBC + oxl;
+      acc0 = acc0 + w * hr[0];
+      acc1 = acc1 + w * hr[kAaBC];
+      acc2 = acc2 + w * hr[2 * kAaBC];
+    }
+  }
+  if (ox < ow && oy < oh) {
+    unsigned char* o = out + (((size_t)f * oh + oy) * ow + ox) * 3;
+    o[0] = (unsigned char)rintf(fminf(fmaxf(acc0, 0.0f), 255.0f));
+    o[1] = (unsigned char)rintf(fminf(fmaxf(acc1, 0.0f), 255.0f));
+    o[2] = (unsigned char)rintf(fminf(fmaxf(acc2, 0.0f), 255.0f));
   }
 }
 
@@ -956,6 +1180,104 @@ int cc_resize_bicubic_u8(const void* in, int n, int src_h, int src_w, void* out,
     hipLaunchKernelGGL(k_resize_bicubic_u8, grid, block, 0,
                        (hipStream_t)stream, (const unsigned char*)in, n, src_h,
                        src_w, (unsigned char*)out, dst_h, dst_w);
+  });
+}
+
+int cc_resize_aa_table_build(int filter, int in_size, int out_size,
+                             int crop_off, int crop_len, void* host_out,
+                             size_t host_out_bytes, int* taps_out) {
+  if (filter != CC_RESIZE_AA_BILINEAR && filter != CC_RESIZE_AA_BICUBIC)
+    return cc::set_error(CC_ERR_INVALID, "resize_aa table: filter must be 0 "
+                         "(bilinear) or 1 (bicubic) (got %d)", filter);
+  if (in_size <= 0 || out_size <= 0)
+    return cc::set_error(CC_ERR_INVALID, "resize_aa table: non-positive size "
+                         "%d -> %d", in_size, out_size);
+  if (crop_off < 0 || crop_len <= 0 || crop_len > out_size - crop_off)
+    return cc::set_error(CC_ERR_INVALID, "resize_aa table: crop [%d, %d+%d) "
+                         "outside [0, %d]", crop_off, crop_off, crop_len,
+                         out_size);
+  // torch's _compute_indices_min_size_weights_aa, align_corners=False, in
+  // double; each weight rounded to f32 once
+  const double interp = filter == CC_RESIZE_AA_BICUBIC ? 4.0 : 2.0;
+  const double scale = (double)in_size / (double)out_size;
+  const double support = scale >= 1.0 ? interp / 2.0 * scale : interp / 2.0;
+  const double invscale = scale >= 1.0 ? 1.0 / scale : 1.0;
+  const double taps_d = 2.0 * ceil(support) + 1.0;
+  if (taps_d > (double)(1 << 24))
+    return cc::set_error(CC_ERR_INVALID, "resize_aa table: %d -> %d needs "
+                         "%.0f taps", in_size, out_size, taps_d);
+  const int taps = (int)taps_d;
+  const size_t bytes = (size_t)crop_len * (2 + (size_t)taps) * 4;
+  if (bytes > (size_t)INT32_MAX)
+    return cc::set_error(CC_ERR_INVALID, "resize_aa table: %zu bytes", bytes);
+  if (taps_out) *taps_out = taps;
+  if (!host_out) return (int)bytes;
+  if (host_out_bytes < bytes)
+    return cc::set_error(CC_ERR_INVALID, "resize_aa table: buffer of %zu "
+                         "bytes, %zu needed", host_out_bytes, bytes);
+  int32_t* first = (int32_t*)host_out;
+  int32_t* count = first + crop_len;
+  float* w = (float*)(count + crop_len);
+  std::vector<double> ws((size_t)taps);
+  for (int n = 0; n < crop_len; n++) {
+    const double center = scale * ((double)(crop_off + n) + 0.5);
+    const int lo = std::max((int)(center - support + 0.5), 0);
+    const int cnt = std::min((int)(center + support + 0.5), in_size) - lo;
+    double total = 0.0;
+    for (int j = 0; j < cnt; j++) {
+      const double x = fabs(((double)(j + lo) - center + 0.5) * invscale);
+      double v = 0.0;
+      if (filter == CC_RESIZE_AA_BILINEAR) {
+        if (x < 1.0) v = 1.0 - x;
+      } else {
+        const double A = -0.5;  // torch's antialias value, not cv2's -0.75
+        if (x < 1.0)
+          v = ((A + 2.0) * x - (A + 3.0)) * x * x + 1.0;
+        else if (x < 2.0)
+          v = A * (((x - 5.0) * x + 8.0) * x - 4.0);
+      }
+      ws[j] = v;
+      total += v;
+    }
+    first[n] = lo;
+    count[n] = cnt;
+    for (int j = 0; j < taps; j++)
+      w[(size_t)n * taps + j] = j < cnt ? (float)(ws[j] / total) : 0.0f;
+  }
+  return (int)bytes;
+}
+
+int cc_resize_aa_u8(const void* in, int n, int src_h, int src_w, void* out,
+                    int out_h, int out_w, const void* table_y_dev, int taps_y,
+                    const void* table_x_dev, int taps_x, uint64_t stream) {
+  if (!in || !out || !table_y_dev || !table_x_dev)
+    return cc::set_error(CC_ERR_INVALID, "resize_aa: null pointer");
+  if (n <= 0 || src_h <= 0 || src_w <= 0 || out_h <= 0 || out_w <= 0 ||
+      taps_y <= 0 || taps_x <= 0)
+    return cc::set_error(CC_ERR_INVALID, "resize_aa: non-positive size n=%d "
+                         "src %dx%d out %dx%d taps %d, %d", n, src_w, src_h,
+                         out_w, out_h, taps_y, taps_x);
+  if ((((size_t)table_y_dev | (size_t)table_x_dev) & 3) != 0)
+    return cc::set_error(CC_ERR_INVALID,
+                         "resize_aa: tables must be 4-byte aligned");
+  if (taps_y > CC_RESIZE_AA_MAX_TAPS || taps_x > CC_RESIZE_AA_MAX_TAPS)
+    return cc::set_error(CC_ERR_UNSUPPORTED, "resize_aa: taps %d, %d above "
+                         "%d", taps_y, taps_x, CC_RESIZE_AA_MAX_TAPS);
+  const long blocks_x = (out_w + kAaBC - 1) / kAaBC;
+  const long bands = (out_h + kAaBR - 1) / kAaBR;
+  const long groups = blocks_x * bands * (long)n;
+  if (groups > (long)INT32_MAX)
+    return cc::set_error(CC_ERR_UNSUPPORTED,
+                         "resize_aa: %ld workgroups do not fit one launch",
+                         groups);
+  return cc::timed_launch("resize_aa_u8", stream, [&] {
+    hipLaunchKernelGGL(k_resize_aa_u8, dim3((unsigned)groups),
+                       dim3(kAaThreads), 0, (hipStream_t)stream,
+                       (const unsigned char*)in, n, src_h, src_w,
+                       (unsigned char*)out, out_h, out_w,
+                       (const int32_t*)table_y_dev, taps_y,
+                       (const int32_t*)table_x_dev, taps_x, (int)blocks_x,
+                       (int)bands);
   });
 }
 

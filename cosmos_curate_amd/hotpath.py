@@ -113,6 +113,12 @@ def _declare(lib: ctypes.CDLL) -> None:
         c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_int, c.c_int,
         c.c_uint64]
     lib.cc_resize_bicubic_u8.argtypes = lib.cc_resize_bilinear_u8.argtypes
+    lib.cc_resize_aa_table_build.argtypes = [
+        c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_size_t,
+        c.POINTER(c.c_int)]
+    lib.cc_resize_aa_u8.argtypes = [
+        c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_int, c.c_int,
+        c.c_void_p, c.c_int, c.c_void_p, c.c_int, c.c_uint64]
     lib.cc_clip_preprocess.argtypes = [
         c.c_void_p, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_float),
         c.POINTER(c.c_float), c.c_void_p, c.c_int, c.c_uint64]
@@ -310,6 +316,131 @@ def yuv_hdr_to_rgb_resize(
     check(load().cc_yuv420sp_hdr_to_rgb_resize(
         y, uv, n, src_h, src_w, pitch_bytes, bit_depth, matrix,
         int(bool(full_range)), tables, inv_w2, out_rgb, out_h, out_w, stream))
+
+
+RESIZE_AA_FILTERS = {"bilinear": 0, "bicubic": 1}  # CC_RESIZE_AA_*
+RESIZE_AA_MAX_TAPS = 129  # CC_RESIZE_AA_MAX_TAPS
+
+
+def _resize_aa_filter(filter: str | int) -> int:
+    if isinstance(filter, str):
+        if filter not in RESIZE_AA_FILTERS:
+            raise ValueError(
+                f"filter must be one of {sorted(RESIZE_AA_FILTERS)}, got {filter!r}")
+        return RESIZE_AA_FILTERS[filter]
+    return int(filter)
+
+
+def resize_aa_table_build(
+    filter: str | int, in_size: int, out_size: int, crop_off: int = 0,
+    crop_len: int | None = None,
+) -> tuple[npt.NDArray[np.uint8], int]:
+    """One axis' table image of cc_resize_aa_table_build as host bytes, and
+    its tap count (host-only, no GPU needed).  The image holds int32
+    first[crop_len], int32 count[crop_len], f32 w[crop_len][taps] for the
+    outputs [crop_off, crop_off + crop_len) of an in_size -> out_size
+    antialiased resize; ``crop_len=None`` means up to out_size.  Raises on
+    arguments the library rejects."""
+    lib = load()
+    if crop_len is None:
+        crop_len = out_size - crop_off
+    f = _resize_aa_filter(filter)
+    taps = ctypes.c_int()
+    nbytes = lib.cc_resize_aa_table_build(
+        f, in_size, out_size, crop_off, crop_len, None, 0, ctypes.byref(taps))
+    if nbytes < 0:
+        check(nbytes)
+    img = np.empty(nbytes, dtype=np.uint8)
+    rc = lib.cc_resize_aa_table_build(
+        f, in_size, out_size, crop_off, crop_len,
+        img.ctypes.data_as(ctypes.c_void_p), nbytes, ctypes.byref(taps))
+    if rc != nbytes:
+        check(rc if rc < 0 else -1)
+    return img, taps.value
+
+
+def resize_aa_geometry(src_h: int, src_w: int, size: int) -> tuple[int, int, int, int]:
+    """(rh, rw, top, left) of torchvision's Resize(size) + CenterCrop(size):
+    the short side becomes ``size``, the long side ``int(size*long/short)``
+    (truncating), the crop sits at ``int(round((resized - size) / 2.0))``
+    with Python's round (half to even)."""
+    if src_h <= 0 or src_w <= 0 or size <= 0:
+        raise ValueError(f"non-positive size {src_h}x{src_w} -> {size}")
+    if src_h <= src_w:
+        rh, rw = size, int(size * src_w / src_h)
+    else:
+        rh, rw = int(size * src_h / src_w), size
+    return rh, rw, int(round((rh - size) / 2.0)), int(round((rw - size) / 2.0))
+
+
+class ResizeAATables:
+    """Both axes' device tables of one (filter, src_h, src_w, size) resize +
+    center crop: ``table_y`` / ``table_x`` (uint8 device tensors), their tap
+    counts and the crop geometry."""
+
+    __slots__ = ("table_y", "table_x", "taps_y", "taps_x", "size",
+                 "resized_h", "resized_w", "top", "left")
+
+    def __init__(self, table_y, table_x, taps_y, taps_x, size, resized_h,
+                 resized_w, top, left) -> None:
+        self.table_y, self.table_x = table_y, table_x
+        self.taps_y, self.taps_x = taps_y, taps_x
+        self.size = size
+        self.resized_h, self.resized_w = resized_h, resized_w
+        self.top, self.left = top, left
+
+
+_resize_aa_tables_dev: dict[tuple[int, int, int, int, int], ResizeAATables] = {}
+
+
+def resize_aa_tables(filter: str | int, src_h: int, src_w: int, size: int) -> ResizeAATables:
+    """The tables of Resize(size, antialias=True) + CenterCrop(size) for
+    (src_h, src_w) frames on the current device, built and uploaded once per
+    (device, filter, src_h, src_w, size).  Raises when an axis needs more
+    taps than the kernel takes (a downscale past 1/32 for bicubic)."""
+    import torch
+
+    f = _resize_aa_filter(filter)
+    key = (torch.cuda.current_device(), f, int(src_h), int(src_w), int(size))
+    tabs = _resize_aa_tables_dev.get(key)
+    if tabs is None:
+        rh, rw, top, left = resize_aa_geometry(src_h, src_w, size)
+        img_y, taps_y = resize_aa_table_build(f, src_h, rh, top, size)
+        img_x, taps_x = resize_aa_table_build(f, src_w, rw, left, size)
+        if max(taps_y, taps_x) > RESIZE_AA_MAX_TAPS:
+            raise ValueError(
+                f"resize {src_h}x{src_w} -> {size} needs {max(taps_y, taps_x)} "
+                f"taps, the kernel takes {RESIZE_AA_MAX_TAPS}")
+        dev = torch.device("cuda", key[0])
+        tabs = ResizeAATables(
+            torch.from_numpy(img_y).to(dev), torch.from_numpy(img_x).to(dev),
+            taps_y, taps_x, int(size), rh, rw, top, left)
+        _resize_aa_tables_dev[key] = tabs
+    return tabs
+
+
+def resize_aa_center_crop(frames_dev_u8, size: int, filter: str | int = "bicubic"):
+    """(n, h, w, 3) u8 on the device -> (n, size, size, 3) u8 on the device:
+    torchvision's Resize(size, antialias=True) + CenterCrop(size) in one
+    kernel that computes only the cropped region (cc_resize_aa_u8).  No
+    fallback: a failing call raises."""
+    import torch
+
+    lib = require_gpu()
+    if (frames_dev_u8.dtype != torch.uint8 or frames_dev_u8.ndim != 4
+            or frames_dev_u8.shape[-1] != 3 or not frames_dev_u8.is_cuda):
+        raise ValueError("frames must be a (n, h, w, 3) uint8 device tensor")
+    n, h, w, _ = frames_dev_u8.shape
+    with torch.cuda.device(frames_dev_u8.device):
+        tabs = resize_aa_tables(filter, h, w, size)
+        src = frames_dev_u8.contiguous()
+        out = torch.empty((n, size, size, 3), dtype=torch.uint8, device=src.device)
+        stream = torch.cuda.current_stream(src.device).cuda_stream
+        check(lib.cc_resize_aa_u8(
+            src.data_ptr(), n, h, w, out.data_ptr(), size, size,
+            tabs.table_y.data_ptr(), tabs.taps_y, tabs.table_x.data_ptr(),
+            tabs.taps_x, stream))
+    return out
 
 
 def estimate_motion(

@@ -10,9 +10,21 @@ ViT forward on the MFMA GEMM path (clip_vit.ClipVisionTowerAMD), bf16.
 At the benchmark config frames arrive already resized to 224x224
 (clip_frame_extraction target_res, SURVEY.md §2 row "Clip frame
 extraction"), so torchvision's Resize/CenterCrop (clip.py:48-56) are
-identity; inputs of other sizes are resized on device with the bicubic
-kernel first (torchvision BICUBIC semantics differ from cv2 INTER_CUBIC
-only in antialias, which is OFF for upscaling and irrelevant at 224->224).
+identity.  Inputs of other sizes (source-resolution frames, target_res -1)
+are resized and center-cropped on device first, by one of two chains:
+
+``resize="cubic"`` (default): cc_resize_bicubic_u8, the cv2 INTER_CUBIC
+kernel (four taps per axis, A = -0.75, no antialiasing), then a crop.  It
+agrees with the reference's chain only where that chain's antialiasing does
+nothing, i.e. when upscaling; on a real downscale a four-tap kernel aliases
+(1080p -> 224 differs from the antialiased result by ~19 codes on average on
+textured content).  Its size arithmetic also rounds where
+torchvision truncates.  Both are kept because a test pins this chain.
+
+``resize="antialias"``: hotpath.resize_aa_center_crop, torchvision's
+Resize(BICUBIC, antialias=True) + CenterCrop with torchvision's size
+arithmetic, bit-exact against tests/resize_aa_ref.py.  SigLIP variants take
+the same chain; HF's squash-to-square SigLIP processor is out of scope.
 """
 
 from __future__ import annotations
@@ -40,16 +52,27 @@ CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 SIGLIP_MEAN = (0.5, 0.5, 0.5)  # SiglipImageProcessor defaults
 SIGLIP_STD = (0.5, 0.5, 0.5)
 
+RESIZE_MODES = ("cubic", "antialias")
+
+
+def check_resize_mode(resize: str) -> str:
+    if resize not in RESIZE_MODES:
+        raise ValueError(f"resize must be one of {RESIZE_MODES}, got {resize!r}")
+    return resize
+
 
 class _CLIPImageEmbeddings(torch.nn.Module):
     """Device-side implementation (reference clip.py:36-74 counterpart)."""
 
     def __init__(self, variant: str = "vit_b32",
-                 checkpoint_path: str | None = None) -> None:
+                 checkpoint_path: str | None = None,
+                 resize: str = "cubic") -> None:
         super().__init__()
         import os
 
         from cosmos_curate_amd.models import clip_weights as cw
+
+        self._resize = check_resize_mode(resize)
 
         hotpath.require_gpu()  # fail loudly before any lazy surprises
         self.device = torch.device("cuda")
@@ -157,7 +180,11 @@ class _CLIPImageEmbeddings(torch.nn.Module):
                     or images.shape[2] != self.tower.cfg.image):
                 # target_res=-1 runs hand source-resolution frames here;
                 # resize+crop on device first (docstring contract above)
-                images = self._resize_center_crop_u8(images)
+                if self._resize == "antialias":
+                    images = hotpath.resize_aa_center_crop(
+                        images, self.tower.cfg.image, "bicubic")
+                else:
+                    images = self._resize_center_crop_u8(images)
             n = images.shape[0]
             patches = self.preprocess_patches_u8(images)
             return self.tower(patches=patches, n=n)
@@ -172,11 +199,16 @@ class CLIPImageEmbeddings(ModelInterface):
     "vit_l14" (the reference's own CLIP model id,
     openai/clip-vit-large-patch14), "siglip_l16_256" or
     "siglip_so400m_14_224" (BASELINE config #3's SigLIP embedder).
+    resize: how frames of another size than the tower's are brought to it,
+    "cubic" (default) or "antialias" (the reference's chain; module
+    docstring).
     """
 
     def __init__(self, variant: str = "vit_b32",
-                 checkpoint_path: str | None = None) -> None:
+                 checkpoint_path: str | None = None,
+                 resize: str = "cubic") -> None:
         super().__init__()
+        self._resize = check_resize_mode(resize)
         self._variant = variant
         self._checkpoint_path = checkpoint_path
         self._model: _CLIPImageEmbeddings | None = None
@@ -191,7 +223,8 @@ class CLIPImageEmbeddings(ModelInterface):
 
     def setup(self) -> None:
         self._model = _CLIPImageEmbeddings(self._variant,
-                                           checkpoint_path=self._checkpoint_path)
+                                           checkpoint_path=self._checkpoint_path,
+                                           resize=self._resize)
 
     def __call__(self, images: torch.Tensor | npt.NDArray[np.uint8]) -> torch.Tensor:
         assert self._model is not None, "setup() not called"

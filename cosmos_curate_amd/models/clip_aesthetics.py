@@ -23,7 +23,7 @@ import torch
 from torch import nn
 
 from cosmos_curate_amd.core.interfaces.model_interface import ModelInterface
-from cosmos_curate_amd.models.clip import CLIPImageEmbeddings
+from cosmos_curate_amd.models.clip import CLIPImageEmbeddings, check_resize_mode
 
 _AESTHETICS_MODEL_ID = "ttj/sac-logos-ava1-l14-linearMSE"
 _CLIP_MODEL_ID = "openai/clip-vit-base-patch32"
@@ -95,8 +95,11 @@ class AestheticScorer(ModelInterface):
 class CLIPAestheticScorer(ModelInterface):
     """clip_aesthetics.py:27-80: frames -> CLIP embeds -> score per frame."""
 
-    def __init__(self) -> None:
+    def __init__(self, resize: str = "cubic") -> None:
+        """``resize``: CLIPImageEmbeddings' keyword, for frames that are not
+        224x224."""
         super().__init__()
+        self._resize = check_resize_mode(resize)
         self._clip_model: CLIPImageEmbeddings | None = None
         self._aesthetic_model: AestheticScorer | None = None
 
@@ -109,7 +112,7 @@ class CLIPAestheticScorer(ModelInterface):
         return [_AESTHETICS_MODEL_ID, _CLIP_MODEL_ID]
 
     def setup(self) -> None:
-        self._clip_model = CLIPImageEmbeddings()
+        self._clip_model = CLIPImageEmbeddings(resize=self._resize)
         self._aesthetic_model = AestheticScorer()
         self._clip_model.setup()
         self._aesthetic_model.setup()

@@ -130,17 +130,22 @@ class ClipEmbeddingStage(CuratorStage):
         log_stats: bool = False,
         variant: str = "vit_b32",
         checkpoint_path: str | None = None,
+        resize: str = "cubic",
     ) -> None:
         """``variant``: the tower, a key of clip_weights.CONFIGS (the
         embedding width follows it: 512 / 768 / 1024 / 1152);
         ``checkpoint_path``: a local checkpoint for it, else the
-        deterministic stand-in weights."""
+        deterministic stand-in weights; ``resize``: how frames of another
+        size than the tower's are brought to it, "cubic" or "antialias"
+        (models/clip.py)."""
+        self._resize = resize
         self._timer = StageTimer(self)
         self._num_gpus = num_gpus_per_worker
         self._batch_size = batch_size
         self._verbose = verbose
         self._log_stats = log_stats
-        self._model = CLIPImageEmbeddings(variant, checkpoint_path=checkpoint_path)
+        self._model = CLIPImageEmbeddings(variant, checkpoint_path=checkpoint_path,
+                                          resize=resize)
 
     @property
     def resources(self) -> CuratorStageResource:

@@ -39,8 +39,12 @@ class AestheticFilterStage(CuratorStage):
         num_gpus_per_worker: float = 0.25,
         verbose: bool = False,
         log_stats: bool = False,
+        resize: str = "cubic",
     ) -> None:
+        """``resize``: how the scorer's CLIP model brings frames that are not
+        224x224 to that size, "cubic" or "antialias" (models/clip.py)."""
         self._timer = StageTimer(self)
+        self._resize = resize
         self._score_threshold = score_threshold
         self._reduction = reduction
         self._num_gpus_per_worker = num_gpus_per_worker
@@ -49,7 +53,7 @@ class AestheticFilterStage(CuratorStage):
         self._frame_extraction_signature = FrameExtractionSignature(
             FrameExtractionPolicy.sequence, target_fps
         ).to_str()
-        self._model = CLIPAestheticScorer()
+        self._model = CLIPAestheticScorer(resize=resize)
         self._reduce_fn = None
 
     @property

@@ -183,7 +183,8 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
         )
 
         stages.append(
-            AestheticFilterStage(score_threshold=args.aesthetic_threshold, log_stats=True)
+            AestheticFilterStage(score_threshold=args.aesthetic_threshold, log_stats=True,
+                                 **_resize_kw(args))
         )
     if args.motion_filter != "disable":
         # MV extraction from codec side data sits behind the rocDecode seam
@@ -232,11 +233,18 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
             log_stats=True,
         ))
         stages.append(ClipEmbeddingStage(
-            log_stats=True, variant=args.embedding_model))
+            log_stats=True, variant=args.embedding_model, **_resize_kw(args)))
     stages.append(ClipWriterStage(
         args.output_clip_path, log_stats=True,
         **({"embedding_algorithm": "internvideo2"} if iv2 else {})))
     return stages
+
+
+def _resize_kw(args: argparse.Namespace) -> dict:
+    """--embedding-resize as the stages' keyword; nothing at the default, so
+    that the default constructs exactly the calls it always did."""
+    resize = getattr(args, "embedding_resize", "cubic")
+    return {} if resize == "cubic" else {"resize": resize}
 
 
 def _setup_parser(parser: argparse.ArgumentParser) -> None:
@@ -271,6 +279,15 @@ def _setup_parser(parser: argparse.ArgumentParser) -> None:
                         "(clip_weights.CONFIGS); frames are resized on device "
                         "to the tower's input size where they differ; "
                         "ignored under --embedding-algorithm internvideo2")
+    parser.add_argument("--embedding-resize", choices=["cubic", "antialias"],
+                        default="cubic",
+                        help="how the image towers (embedding and aesthetics) "
+                        "bring frames of another size to their input size: "
+                        "cubic is the four-tap cv2-style kernel, antialias is "
+                        "torchvision's Resize(BICUBIC, antialias=True) + "
+                        "CenterCrop, what source-resolution frames "
+                        "(--clip-extraction-target-res -1) want; ignored "
+                        "under --embedding-algorithm internvideo2")
     parser.add_argument("--aesthetic-threshold", type=float, default=None)
     parser.add_argument("--clip-extraction-target-res", type=int, default=224,
                         help="square target resolution for extracted frames; "
@@ -323,9 +340,13 @@ def split(args: argparse.Namespace, runner: RunnerInterface | None = None) -> di
         for st in stages:
             inner = st.stage if hasattr(st, "stage") else st
             hdr = getattr(inner, "_hdr", "off")
-            print(type(inner).__name__ if hdr == "off" else
-                  f"{type(inner).__name__} hdr={hdr} "
-                  f"hdr_peak_nits={inner._hdr_peak_nits:g}")
+            resize = getattr(inner, "_resize", "cubic")
+            line = type(inner).__name__
+            if hdr != "off":
+                line += f" hdr={hdr} hdr_peak_nits={inner._hdr_peak_nits:g}"
+            if resize != "cubic":
+                line += f" resize={resize}"
+            print(line)
         return {"dry_run": True, "num_input_videos": len(input_tasks),
                 "num_stages": len(stages)}
     save_cfg = None

@@ -245,6 +245,51 @@ int cc_resize_bilinear_u8(const void* in, int n, int src_h, int src_w,
 /* u8 NHWC bicubic resize, A=-0.75 (cv2 INTER_CUBIC semantics). */
 int cc_resize_bicubic_u8(const void* in, int n, int src_h, int src_w,
                          void* out, int dst_h, int dst_w, uint64_t stream);
+/* ---- antialiased separable resize + crop ----
+ * torchvision's Resize(size, BICUBIC | BILINEAR, antialias=True) followed by
+ * CenterCrop, computing only the cropped region; written definition and
+ * bit-exact reference: tests/resize_aa_ref.py.
+ *
+ * cc_resize_aa_table_build writes one axis' table for the outputs
+ * [crop_off, crop_off + crop_len) of an in_size -> out_size resize, by
+ * torch's _compute_indices_min_size_weights_aa (align_corners=False), in
+ * double with each weight rounded to f32 once:
+ *   scale = in/out; support = (interp/2)*scale if scale >= 1 else interp/2
+ *   (interp 4 bicubic, 2 bilinear); taps = 2*ceil(support) + 1;
+ *   center = scale*(i + 0.5); first = max(int(center - support + 0.5), 0);
+ *   count = min(int(center + support + 0.5), in) - first;
+ *   w[j] = filter((j + first - center + 0.5)*invscale) / sum.
+ * bicubic uses A = -0.5 (torch's antialias value).  Layout: int32
+ * first[crop_len], int32 count[crop_len], f32 w[crop_len][taps], weights
+ * past count zero.  Host-only, touches no device.  Returns the image's size
+ * in bytes (positive) and *taps; with host_out == NULL it only does that.
+ * CC_ERR_INVALID on an unknown filter, non-positive sizes, a crop outside
+ * [0, out_size] or a buffer smaller than the image. */
+enum { CC_RESIZE_AA_BILINEAR = 0, CC_RESIZE_AA_BICUBIC = 1 };
+#define CC_RESIZE_AA_MAX_TAPS 129
+int cc_resize_aa_table_build(int filter, int in_size, int out_size,
+                             int crop_off, int crop_len, void* host_out,
+                             size_t host_out_bytes, int* taps);
+/* u8 NHWC (n, src_h, src_w, 3) -> u8 NHWC (n, out_h, out_w, 3) through two
+ * device copies of such tables (4-byte aligned; table_y for out_h rows,
+ * table_x for out_w columns).  Per output and channel, f32, multiply then
+ * add without contraction, k ascending from 0.0f:
+ *   hrow[y] = sum_k wx[ox][k] * float(src[y][firstx[ox] + k])
+ *   v       = sum_k wy[oy][k] * hrow[firsty[oy] + k]
+ *   out     = u8(rintf(min(max(v, 0), 255)))        (half to even)
+ * The kernel is the same for every filter and every tap count up to
+ * CC_RESIZE_AA_MAX_TAPS (bicubic down to 1/32): horizontal sums are staged
+ * in LDS per band of output rows, in as many chunks of source rows as the
+ * band needs.  The launcher cannot read the tables, so the kernel does not
+ * trust them: it clamps first to [0, src] and count to [0, min(taps, src -
+ * first)] where it reads them, which leaves a table of the builder's as it
+ * is and keeps any other inside the source.  Before any launch:
+ * CC_ERR_INVALID on null or misaligned pointers and non-positive sizes or
+ * taps, CC_ERR_UNSUPPORTED on taps above CC_RESIZE_AA_MAX_TAPS or more than
+ * 2^31-1 workgroups.  Timed as "resize_aa_u8". */
+int cc_resize_aa_u8(const void* in, int n, int src_h, int src_w, void* out,
+                    int out_h, int out_w, const void* table_y_dev, int taps_y,
+                    const void* table_x_dev, int taps_x, uint64_t stream);
 /* (N,H,W,3) u8 -> (N,3,H,W) normalized ((x/255)-mean)/std.
  * out_dtype: 0 = f32, 1 = bf16. */
 int cc_clip_preprocess(const void* in, int n, int h, int w,
