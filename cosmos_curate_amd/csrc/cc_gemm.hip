@@ -307,7 +307,7 @@ constexpr int NFR2 = WN2 / FRAG;  // 4
 // (mean, rstd) pairs are a 2 KB LDS table behind the 128 KiB of operand
 // buffers, staged like the operands: one 4-byte-wide glds per wave (its
 // 32 rows), issued with the tile's prologue, landed by the rep-top
-// vmcnt(0) and published by the rep-top barrier; the epilogue reads it.
+// wait and published by the rep-top barrier; the epilogue reads it.
 // No VGPR carries it (a register-held pair was spilled around the
 // epilogue and its vmcnt(0) exposed one load latency per tile).  TWO
 // tables, alternating per tile: tile r+1's glds is issued before tile r's
@@ -321,7 +321,57 @@ constexpr int NFR2 = WN2 / FRAG;  // 4
 // the staged read-back 8 adjacent lanes hold one row's 64 columns, so it
 // is 3 DPP adds per value, no LDS, no barrier.  Needs N % 64 == 0.
 // LN_IN and STATS launches are bf16-out and always staged.
+//
+// Column tables: the tile's 256 bias values, and under
+// LN_IN its 256 column sums, are staged the same way, 2 KB per tile: wave w
+// fills floats [64 w, 64 w + 64) with one 4-byte-wide glds, waves 0-3 the
+// bias of the tile's columns, waves 4-7 the column sums (the bias again
+// without LN_IN, so every wave issues the same number of loads and the
+// hand-counted waits of the epilogue hold for all of them).  The column is
+// clamped like the A rows; the store is what is predicated.  A plain
+// VGPR-destination load here would make hipcc drain the whole prologue
+// burst with vmcnt(0) (it waits that way for any ordinary load issued
+// beside LDS-DMA).  TWO tables, alternating per tile, for the reason the
+// (mean, rstd) tables alternate: tile r+1's glds is issued before tile r's
+// epilogue reads table r.  Table (r+1)&1 was last read in epilogue r-1,
+// which every wave left before any wave passed rep-top barrier r, and the
+// glds is issued after that.
 constexpr int LN_TAB = BM2 * 4;  // one table: 256 float2 = 2 KB, in bf16 elements
+constexpr int COL_TAB = BN2 * 4;  // bias[256] + colsum[256] floats = 2 KB
+
+// 16 B from global memory, invisible to hipcc's wait bookkeeping: the
+// caller waits with a hand-counted vmcnt (res_wait below) before the first
+// use
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+// (base must be wave-uniform: it is the scalar half of the address)
+__device__ __forceinline__ void load16_uncounted(u32x4& dst, const void* base,
+                                                 unsigned byte_off) {
+  // s_nop 4: the base may come straight from a v_readfirstlane, and hipcc
+  // pads no hazard for an instruction inside an asm string
+  asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2"
+               : "=v"(dst)
+               : "v"(byte_off), "s"(base)
+               : "memory");
+}
+// The wait for a pass's 4 loads: vmcnt(CNT_NEXT) when the next tile's
+// prologue is in the queue, vmcnt(CNT_LAST) when it is not, then ONE
+// statement that takes the four destinations "+v", so that no use of them
+// is scheduled above it.  The wait statements themselves name no register:
+// with the registers tied to two alternative statements hipcc copied them
+// into each statement's own operands ahead of the wait, reading them before
+// the data had landed.  Any copy it makes for the one statement below sits
+// behind the wait.
+template <int CNT_NEXT, int CNT_LAST>
+__device__ __forceinline__ void res_wait(bool has_next, u32x4 (&r)[4]) {
+  static_assert(CNT_NEXT >= CNT_LAST && CNT_LAST >= 0 && CNT_NEXT < 64,
+                "vmcnt is a 6-bit field");
+  if (has_next)
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT_NEXT) : "memory");
+  else
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT_LAST) : "memory");
+  asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3])::"memory");
+}
 
 // v + (the same value in the lane DPP control CTRL names)
 template <int CTRL>
@@ -350,15 +400,40 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
   // WG per CU) around the round-1 8-phase glds schedule.  Each WG walks
   // tiles bid, bid+grid, ... and issues the NEXT tile's 12-glds
   // prologue BEFORE the epilogue stores, so prologue HBM latency hides
-  // under the C writeback instead of stalling a fresh WG.  Measured
+  // under the C writeback instead of stalling a fresh WG (it does only
+  // because nothing in the staged epilogue makes hipcc wait vmcnt(0)
+  // after it: see the epilogue).  Measured
   // +18-27% at every batch-64 ViT shape and +13% at square8k
   // (profiles/r02_gemm_persist.log: fc1 711->874, fc2 795->968, patch
   // 814->964, qkv 724->887 TF within one box).  order_mode: 0 = plain
   // stride; 1 = stride + bijective XCD remap (skinny-N grids, L2 row
   // sharing).  Sync structure per K-tile is UNCHANGED from the
   // race-screened v11 (vmcnt(0) publish at ph3, leading barriers).
-  // 128 KiB (+ the two 2 KB (mean, rstd) tables under LN_IN)
-  __shared__ __bf16 lds[2 * (BM2 + BN2) * BK + (LN_IN ? 2 * LN_TAB : 0)];
+  static_assert(!LN_IN || HAS_BIAS, "the folded norm always carries a bias");
+  // a launch with a bias stages the column tables, whichever epilogue its
+  // output type then takes
+  constexpr bool COLTAB = HAS_BIAS;
+  // 128 KiB (+ the two 2 KB (mean, rstd) tables under LN_IN, + the two
+  // 2 KB column tables with a bias: 136 KiB at the most)
+  __shared__ __bf16 lds[2 * (BM2 + BN2) * BK + (LN_IN ? 2 * LN_TAB : 0) +
+                        (COLTAB ? 2 * COL_TAB : 0)];
+// column table b; this wave stages floats [64 wid, 64 wid + 64) of it
+#define COLTAB_AT(b)                                                        \
+  ((float*)(lds + 2 * (BM2 + BN2) * BK + (LN_IN ? 2 * LN_TAB : 0) +         \
+            (b) * COL_TAB))
+#define STAGE_COL2(b)                                                       \
+  do {                                                                      \
+    if constexpr (COLTAB) {                                                 \
+      const long c = bn + (wid & 3) * 64 + lane;                            \
+      const float* g = ((LN_IN && wid >= 4) ? colsum : bias) +              \
+                       (c < N ? c : N - 1);                                 \
+      __builtin_amdgcn_global_load_lds(                                     \
+          (const __attribute__((address_space(1))) unsigned int*)g,         \
+          (__attribute__((address_space(3))) unsigned int*)(COLTAB_AT(b) +  \
+                                                            wid * 64),      \
+          4, 0, 0);                                                         \
+    }                                                                       \
+  } while (0)
 // table b; this wave stages dwords [64 wid, 64 wid + 64) of it: dword d is
 // component d & 1 of tile row d >> 1, the row clamped like the A rows
 #define LNTAB(b) ((float*)(lds + 2 * (BM2 + BN2) * BK + (b) * LN_TAB))
@@ -407,6 +482,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
   // first prologue: A(0) h0,h1, B(0) h0,h1, B(1) h0,h1 (12 glds); later
   // tiles' prologues issue under the previous epilogue.
   STAGE_LN2(0);
+  STAGE_COL2(0);
   STAGE_A2(0, 0);
   STAGE_A2(0, 1);
   STAGE_B2(0, 0);
@@ -414,13 +490,40 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
   STAGE_B2(1, 0);
   STAGE_B2(1, 1);
 
+  // glds of one prologue per wave, and stores of one staged epilogue per
+  // wave: 4 passes x 4 chunks, each one C store (+ one stats store).  Both
+  // are the same for every wave and every tile (the stores are issued
+  // unconditionally and range-checked by the hardware), which is what lets
+  // the waits below be counted.
+  constexpr int PRO_LOADS = 12 + (LN_IN ? 1 : 0) + (COLTAB ? 1 : 0);
+  constexpr int PASS_STORES = STATS ? 8 : 4;
+  const bool staged = (c_is_bf16 && EPI_STAGED) || LN_IN || STATS;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the first prologue
+
   for (int rep = 0; rep < tiles; rep++) {
     if ((int)blockIdx.x + rep * (int)gridDim.x >= nwg) break;
     f32x4 acc[MFR2][NFR2] = {};
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // rep-top drain: the
-    __builtin_amdgcn_s_barrier();  // one full drain left (covers the 12
-    // prologue glds AND the previous epilogue's in-flight stores; a
-    // counted form here would need codegen-dependent store counts)
+    // rep-top wait: land this tile's prologue, then publish it with the
+    // barrier.  After a staged epilogue the queue is, youngest first,
+    // [C/stats stores of the 4 passes : 4 PASS_STORES, prologue :
+    // PRO_LOADS, <older>], so vmcnt(4 PASS_STORES) retires the prologue and
+    // leaves the stores in flight: their acknowledgement is not waited for
+    // here.  They retire at the first K-tile's counted waits, which they
+    // are older than.  Nothing needs them sooner: a store's data is read
+    // from its registers when it issues; the staging slice (A-buf1) was
+    // read back by ds_read, and that data waited for, before the store it
+    // fed; and the next tile writes only A-buf0 and the B-bufs until
+    // STAGE_A2(1, .) in its first K-tile, which sits behind this barrier
+    // and the epilogue's last ds_read.  The scalar epilogue's store count
+    // is the compiler's business, so it drains; the first tile has no
+    // stores ahead of it and drained before the loop.
+    if (rep > 0) {
+      if (staged)
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * PASS_STORES) : "memory");
+      else
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_s_barrier();
 
 #define PHASE_MFMA2(q)                                                      \
   do {                                                                      \
@@ -480,8 +583,12 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
     const __bf16* Bt = B2T((t) & 1);                                        \
     /* no-op since the publish below moved back before the barrier (the */ \
     /* queue holds only B(t+1):4 here, or nothing at tile 0 of a rep);  */ \
-    /* kept as the compiler fence the measured schedule was built with  */ \
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                        \
+    /* kept as the compiler fence the measured schedule was built with. */ \
+    /* At tile 0 of a later rep the queue holds the previous epilogue's */ \
+    /* stores instead, which nothing here depends on: the count lets    */ \
+    /* them all stand, so they retire at the publish below              */ \
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 + 4 * PASS_STORES)           \
+                 : "memory");                                               \
     READ_B2(Bt);                                                            \
     READ_A2(At, 0);                                                         \
     if ((t) + 1 < KT) STAGE_A2((t) + 1, 0);                                 \
@@ -538,22 +645,82 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
     // reading in the last phase; the next tile's prologue (further
     // below) overwrites A-buf0/B-bufs with the same hazard.
     __builtin_amdgcn_s_barrier();
-    // advance + issue the next tile's prologue BEFORE the epilogue so
-    // its 12-glds HBM latency hides under the C writeback.
-    if (rep + 1 < tiles &&
-        (int)blockIdx.x + (rep + 1) * (int)gridDim.x < nwg) {
-      int orig = (int)blockIdx.x + (rep + 1) * (int)gridDim.x;
-      if (order_mode == 1) orig = xcd_remap(orig, nwg);
-      bm = (long)(orig / nbx) * BM2;
-      bn = (long)(orig % nbx) * BN2;
-      STAGE_LN2((rep + 1) & 1);
-      STAGE_A2(0, 0);
-      STAGE_A2(0, 1);
-      STAGE_B2(0, 0);
-      STAGE_B2(0, 1);
-      STAGE_B2(1, 0);
-      STAGE_B2(1, 1);
-    }
+    // From here to the end of the tile every lane-dependent value is
+    // derived again from an opaque copy of the thread id.  Derived from
+    // `tid` itself, the address parts the epilogue and the next prologue
+    // need (and the K-loop does not) are hoisted out of the rep loop, held
+    // across the K-loop, spilled there, and reloaded here: a scratch
+    // reload is a VGPR-destination load, so each one costs a vmcnt(0) in
+    // the middle of the prefetch.
+    int tid_e = tid;
+    asm volatile("" : "+v"(tid_e));
+    {  // NOLINT: shadows on purpose
+    const int tid = tid_e, lane = tid_e & 63, wid = tid_e >> 6;
+    const int waveM = wid >> 2, waveN = wid & 3;
+    const long srow = wid * 16;
+    const bool has_next = rep + 1 < tiles &&
+                          (int)blockIdx.x + (rep + 1) * (int)gridDim.x < nwg;
+    // Residual of the staged epilogue: pass p (32 tile rows of this wave)
+    // adds 4 chunks of 16 B per lane, resq[p][0..3].  The loads are
+    // branch-free (row and column clamped like stage_rows clamps: an
+    // out-of-range lane loads a value that is never stored) and hidden
+    // from hipcc in asm, which would otherwise wait vmcnt(0) for each one
+    // beside the LDS-DMA in flight, draining the prologue below and taking
+    // one HBM round trip per chunk, 16 per tile.  Passes 0-2 are issued
+    // HERE, ahead of the prologue: the counter retires in issue order, so
+    // whatever is issued after the prologue burst waits for all of it.
+    // afrag and bfragT are dead, which is the 48 VGPRs the 12 loads take.
+    // Pass 3 is issued after pass 0's write phase has freed a quarter of
+    // the accumulators.
+    //
+    // Addressing of the read-back (loads and stores alike): chunk i of
+    // pass p is 8 columns of tile row waveM 128 + 32 p + 8 i + lane / 8.
+    // Everything is a 32-bit element offset from the tile's first row
+    // (at most 256 N), on a wave-uniform 64-bit base, so no 64-bit lane
+    // value is live across the K-loop.  row_off is made opaque here: the
+    // 16 row offsets derived from it do not depend on the tile, and hoisted
+    // out of the rep loop they are spilled, each reload a vmcnt(0).
+    const int n32 = (int)N;
+    const int tile_rows = (int)((M - ebm) < BM2 ? (M - ebm) : BM2);
+    int row_off = (waveM * WM2 + (lane >> 3)) * n32;
+    asm volatile("" : "+v"(row_off));
+    const int col_abs = (int)ebn + waveN * WN2 + (lane & 7) * 8;
+    u32x4 resq[4][4];
+    auto issue_res = [&](int p) {
+      if constexpr (HAS_RES) {
+        const __bf16* rbase = residual + ebm * N;  // wave-uniform
+        const int last_row = (tile_rows - 1) * n32;
+        const int col = col_abs < n32 ? col_abs : n32 - 8;  // N % 8 == 0
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int ro = row_off + (p * 32 + i * 8) * n32;
+          load16_uncounted(resq[p][i], rbase,
+                           ((ro < last_row ? ro : last_row) + col) * 2);
+        }
+      }
+    };
+    // advance + issue the next tile's prologue BEFORE the epilogue's
+    // write phase, so its HBM latency hides under the C writeback.  Each
+    // epilogue calls it itself: the staged one after its first residual
+    // loads, whose registers then live in that branch alone (live across
+    // the join of a common call they were spilled straight after the
+    // loads were issued, before the data had landed).
+    auto next_prologue = [&] {
+      if (has_next) {
+        int orig = (int)blockIdx.x + (rep + 1) * (int)gridDim.x;
+        if (order_mode == 1) orig = xcd_remap(orig, nwg);
+        bm = (long)(orig / nbx) * BM2;
+        bn = (long)(orig % nbx) * BN2;
+        STAGE_LN2((rep + 1) & 1);
+        STAGE_COL2((rep + 1) & 1);
+        STAGE_A2(0, 0);
+        STAGE_A2(0, 1);
+        STAGE_B2(0, 0);
+        STAGE_B2(0, 1);
+        STAGE_B2(1, 0);
+        STAGE_B2(1, 1);
+      }
+    };
 
     // ---- epilogue ----
     // bf16 output (all tower-internal GEMMs): LDS-staged + coalesced.
@@ -572,28 +739,47 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
     // the scalar path, inside the embedding-cosine contract.
     const long crow_base = ebm + waveM * WM2 + 4 * (lane >> 4);
     const long ccol_base = ebn + waveN * WN2 + (lane & 15);
-    if ((c_is_bf16 && EPI_STAGED) || LN_IN || STATS) {
+    if (staged) {
+      issue_res(0);
+      issue_res(1);
+      issue_res(2);
+      next_prologue();
       __bf16* slice = A2T(1) + wid * 2048;  // 4 KB per wave
-      const long wrow0 = ebm + waveM * WM2;
-      const long wcol0 = ebn + waveN * WN2;
-      // bias depends only on the n-fragment: 4 loads per lane, hoisted
-      // out of the 4x2 pass loop (was reloaded 8x)
+      // bias and column sum depend only on the n-fragment: 4 values per
+      // lane each, read from this tile's column table (landed by the
+      // rep-top wait, published by the rep-top barrier)
       float bhoist[NFR2] = {};
-      if constexpr (HAS_BIAS) {
-#pragma unroll
-        for (int n = 0; n < NFR2; n++) {
-          const long col = ccol_base + n * FRAG;
-          bhoist[n] = (col < N) ? bias[col] : 0.0f;
-        }
-      }
       float shoist[NFR2] = {};  // LN_IN: column sums of the folded weight
-      if constexpr (LN_IN) {
+      if constexpr (COLTAB) {
+        const float* ct = COLTAB_AT(rep & 1) + waveN * WN2 + (lane & 15);
 #pragma unroll
         for (int n = 0; n < NFR2; n++) {
-          const long col = ccol_base + n * FRAG;
-          shoist[n] = (col < N) ? colsum[col] : 0.0f;
+          bhoist[n] = ct[n * FRAG];
+          if constexpr (LN_IN) shoist[n] = ct[BN2 + n * FRAG];
         }
       }
+      // Stores: one descriptor per tile for C (and one for the stats),
+      // base = the tile's first row, num_records = the bytes of the rows
+      // of this tile that exist.  A lane's byte offset is (tile row, column),
+      // so a row >= M lies beyond num_records and the hardware drops the
+      // store; a column >= N, or a stats lane that is not its group's
+      // leader, is sent there by a select.  Every wave therefore issues the
+      // same 4 (8) stores per pass whatever the tile, no branch around any
+      // of them, and the offsets stay far below 4 GB however large C is.
+      // Built from wave-uniform values only.
+      constexpr unsigned OOB = 0x80000000u;
+      const __amdgpu_buffer_rsrc_t c_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+          (__bf16*)C + ebm * N, 0, tile_rows * n32 * 2, 0x00020000);
+      __amdgpu_buffer_rsrc_t s_rsrc = c_rsrc;
+      if constexpr (STATS)
+        s_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+            stats + ebm * (N >> 6), 0, tile_rows * (n32 >> 6) * 8, 0x00020000);
+      // Hand-counted waits of the residual passes.  Issue order per wave:
+      //   R0 R1 R2 (4 loads each) | prologue (PRO, or nothing after the
+      //   last tile) | pass 0 write phase | R3 | wait R0, St0 | wait R1,
+      //   St1 | wait R2, St2 | wait R3, St3       (St = PASS_STORES)
+#define RES_WAIT(p, cnt)                                                    \
+  res_wait<(cnt) + PRO_LOADS, (cnt)>(has_next, resq[p])
 #pragma unroll
       for (int p = 0; p < 4; p++) {
 #pragma unroll
@@ -601,10 +787,15 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
           const int m = 2 * p + mm;
           float2 mr[4] = {};  // LN_IN: (mean, rstd) of this lane's 4 rows
           if constexpr (LN_IN) {
-            const float2* t = (const float2*)LNTAB(rep & 1) + waveM * WM2 +
-                              m * FRAG + 4 * (lane >> 4);
+            // read as float, not float2: hipcc puts a vmcnt(0) in front
+            // of an LDS read that its type-based alias analysis cannot
+            // tell from the LDS-DMA in flight (the prologue's), and it can
+            // tell a float from the DMA's dwords but not a HIP vector type
+            const float* t = LNTAB(rep & 1) +
+                             2 * (waveM * WM2 + m * FRAG + 4 * (lane >> 4));
 #pragma unroll
-            for (int r = 0; r < 4; r++) mr[r] = t[r];
+            for (int r = 0; r < 4; r++)
+              mr[r] = make_float2(t[2 * r], t[2 * r + 1]);
           }
 #pragma unroll
           for (int n = 0; n < NFR2; n++) {
@@ -621,63 +812,78 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
             }
           }
         }
+        if constexpr (HAS_RES) {
+          if (p == 0) {
+            issue_res(3);
+            // youngest first: [R3:4, PRO, R2:4, R1:4, R0]
+            RES_WAIT(0, 12);
+          } else if (p == 1) {
+            // [St0, R3:4, PRO, R2:4, R1]
+            RES_WAIT(1, PASS_STORES + 8);
+          } else if (p == 2) {
+            // [St1, St0, R3:4, PRO, R2]
+            RES_WAIT(2, 2 * PASS_STORES + 4);
+          } else {
+            // [St2, St1, St0, R3]; the prologue is older than R3 and
+            // retires with it
+            res_wait<3 * PASS_STORES, 3 * PASS_STORES>(has_next, resq[3]);
+          }
+        }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
         for (int i = 0; i < 4; i++) {
           const int elem = i * 512 + lane * 8;
-          const int lrow = elem >> 6;          // /64
-          const int lcol8 = elem & 63;         // 8-elem aligned
-          const long grow = wrow0 + p * 32 + lrow;
-          const long gcol = wcol0 + lcol8;
-          if constexpr (STATS) {
-            // the 8 lanes of a row share grow and (N % 64 == 0) the side
-            // of the N edge, so `ok` is uniform over each sum8 group; the
-            // adds run on every lane, outside the branch
-            const bool ok = grow < M && gcol < N;
-            float s = 0.0f, ss = 0.0f;
-            if (ok) {
-              bf16x8 v8 = *(const bf16x8*)(slice + elem);
-              const bf16x8 r8 = *(const bf16x8*)(residual + grow * N + gcol);
+          const int ro = row_off + (p * 32 + i * 8) * n32;  // tile row x N
+          const bool col_ok = col_abs < n32;  // N % 8 == 0 always
+          const unsigned c_off = col_ok ? (unsigned)(ro + col_abs) * 2 : OOB;
+          bf16x8 v8 = *(const bf16x8*)(slice + elem);
+          float s = 0.0f, ss = 0.0f;
+          if constexpr (HAS_RES) {
+            const bf16x8 r8 = __builtin_bit_cast(bf16x8, resq[p][i]);
 #pragma unroll
-              for (int e = 0; e < 8; e++) {
-                v8[e] = (__bf16)((float)v8[e] + (float)r8[e]);
+            for (int e = 0; e < 8; e++) {
+              v8[e] = (__bf16)((float)v8[e] + (float)r8[e]);
+              if constexpr (STATS) {
                 const float f = (float)v8[e];
                 s += f;
                 ss += f * f;
               }
-              *(bf16x8*)((__bf16*)C + grow * N + gcol) = v8;
             }
+          }
+          __builtin_amdgcn_raw_buffer_store_b128(
+              __builtin_bit_cast(u32x4, v8), c_rsrc, (int)c_off, 0, 0);
+          if constexpr (STATS) {
+            // the 8 lanes of a row hold its 64 columns (N % 64 == 0, so
+            // they share the side of the N edge); lanes whose row or
+            // column is out of range sum values that are never stored
             s = sum8(s);
             ss = sum8(ss);
-            if (ok && (lane & 7) == 0)
-              stats[grow * (N >> 6) + (gcol >> 6)] = make_float2(s, ss);
-            continue;
+            const unsigned s_off =
+                (col_ok && (lane & 7) == 0)
+                    ? (unsigned)((ro + col_abs) >> 6) * 8
+                    : OOB;
+            u32x2 st;
+            st[0] = __builtin_bit_cast(unsigned, s);
+            st[1] = __builtin_bit_cast(unsigned, ss);
+            __builtin_amdgcn_raw_buffer_store_b64(st, s_rsrc, (int)s_off, 0, 0);
           }
-          if (grow >= M || gcol >= N) continue;  // N % 8 == 0 always
-          bf16x8 v8 = *(const bf16x8*)(slice + elem);
-          if constexpr (HAS_RES) {
-            const bf16x8 r8 =
-                *(const bf16x8*)(residual + grow * N + gcol);
-#pragma unroll
-            for (int e = 0; e < 8; e++)
-              v8[e] = (__bf16)((float)v8[e] + (float)r8[e]);
-          }
-          *(bf16x8*)((__bf16*)C + grow * N + gcol) = v8;
         }
       }
+#undef RES_WAIT
     } else {
       // scalar store path (f32 outputs always; bf16 when epi_staged=0).
       // bias hoisted exactly like the staged path: 4 loads per lane
       // instead of one dependent load per fragment (the old
       // per-element-load serialization, guide trap (c)).
+      next_prologue();
       const bool interior = (ebm + BM2 <= M) && (ebn + BN2 <= N);
       float bhoist2[NFR2] = {};
       if constexpr (HAS_BIAS) {
+        // from the column table as well (a column >= N reads a clamped
+        // value that is never stored)
+        const float* ct = COLTAB_AT(rep & 1) + waveN * WN2 + (lane & 15);
 #pragma unroll
-        for (int n = 0; n < NFR2; n++) {
-          const long col = ccol_base + n * FRAG;
-          bhoist2[n] = (interior || col < N) ? bias[col] : 0.0f;
-        }
+        for (int n = 0; n < NFR2; n++) bhoist2[n] = ct[n * FRAG];
       }
 #pragma unroll
       for (int m = 0; m < MFR2; m++) {
@@ -700,9 +906,12 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
         }
       }
     }
+    }  // lane-dependent values of the epilogue
   }
 #undef LNTAB
 #undef STAGE_LN2
+#undef COLTAB_AT
+#undef STAGE_COL2
 #undef A2T
 #undef B2T
 #undef STAGE_A2
