@@ -10,6 +10,8 @@ Per-file flags:
   change rounding.
 - cc_gemm.hip: default contraction (MFMA does the math anyway).
 - cc_motion.hip: integer arithmetic only; no floating-point flags matter.
+- cc_conv.hip: default contraction (MFMA, and an FMA first layer whose
+  tolerance is the f32 accumulation bound, not bit-exactness).
 """
 
 from __future__ import annotations
@@ -35,6 +37,7 @@ SOURCES: list[tuple[str, list[str]]] = [
     ("cc_ln.hip", [ARCH]),
     ("cc_attn.hip", [ARCH]),
     ("cc_motion.hip", [ARCH]),
+    ("cc_conv.hip", [ARCH]),
 ]
 
 

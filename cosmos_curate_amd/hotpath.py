@@ -186,6 +186,18 @@ def _declare(lib: ctypes.CDLL) -> None:
         c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_float, c.c_uint64]
     lib.cc_pairwise_max_earlier.argtypes = [
         c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_uint64]
+    lib.cc_conv3x3_bf16.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int,
+        c.c_int, c.c_int, c.c_uint64]
+    lib.cc_conv3x3_u8.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int,
+        c.c_int, c.c_uint64]
+    lib.cc_tconv3_bf16.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64,
+        c.c_int, c.c_int, c.c_int, c.c_uint64]
+    lib.cc_avgpool2x2_bf16.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int, c.c_int,
+        c.c_uint64]
 
     lib.cc_timing_enable.argtypes = [c.c_int]
     lib.cc_timing_report.argtypes = [
@@ -466,6 +478,40 @@ def estimate_motion(
         cur_ptr, ref_ptr, n, h, w, pitch_bytes, frame_stride_bytes,
         1 if bit_depth == 8 else 2, search_range, mv_lambda, mv_out_ptr,
         cost_out_ptr or None, stream))
+
+
+def conv3x3_bf16(x_ptr: int, w_ptr: int, y_ptr: int, frames: int, h: int,
+                 w: int, cin: int, cout: int, stream: int) -> None:
+    """3x3 spatial conv, zero padding 1, on bf16 channels-last device
+    pointers (cc_conv3x3_bf16): x [frames,h,w,cin], weights
+    [cout][3][3][cin], y [frames,h,w,cout].  No fallback: a failing call
+    raises."""
+    check(load().cc_conv3x3_bf16(x_ptr, w_ptr, y_ptr, frames, h, w, cin, cout,
+                                 stream))
+
+
+def conv3x3_u8(x_ptr: int, w_ptr: int, y_ptr: int, frames: int, h: int,
+               w: int, cout: int, stream: int) -> None:
+    """The same conv for a 3-channel u8 input taken as bf16(x/255)
+    (cc_conv3x3_u8): x u8 [frames,h,w,3], weights bf16 [cout][3][3][3]."""
+    check(load().cc_conv3x3_u8(x_ptr, w_ptr, y_ptr, frames, h, w, cout, stream))
+
+
+def tconv3_bf16(x_ptr: int, w_ptr: int, bias_ptr: int, shortcut_ptr: int,
+                y_ptr: int, b: int, t: int, hw: int, f: int,
+                stream: int) -> None:
+    """Four-branch dilated temporal conv + bias + relu (+ shortcut) on
+    device pointers (cc_tconv3_bf16): x [b,t,hw,8f], weights [4][f][3][2f],
+    bias f32 [4f], y [b,t,hw,4f]; ``shortcut_ptr`` 0 for none."""
+    check(load().cc_tconv3_bf16(x_ptr, w_ptr, bias_ptr, shortcut_ptr or None,
+                                y_ptr, b, t, hw, f, stream))
+
+
+def avgpool2x2_bf16(x_ptr: int, y_ptr: int, frames: int, h: int, w: int,
+                    c: int, stream: int) -> None:
+    """2x2 average pool of bf16 channels-last frames, odd sizes floored
+    (cc_avgpool2x2_bf16): [frames,h,w,c] -> [frames,h//2,w//2,c]."""
+    check(load().cc_avgpool2x2_bf16(x_ptr, y_ptr, frames, h, w, c, stream))
 
 
 def gemm_plan(

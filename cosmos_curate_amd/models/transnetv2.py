@@ -10,8 +10,14 @@ interchange; parity vs the reference implementation is pinned by committed
 golden vectors (tests/golden/transnetv2_golden.npz, generated in the dev
 container by oracle/gen_transnet_golden.py).
 
-The network is tiny ((1,100,27,48,3) input) and runs on torch-rocm/MIOpen
-(not kernel-worthy).  Published weights
+The default route runs the network as f32 ``nn.Conv3d`` on
+torch-rocm/MIOpen, one (1,100,27,48,3) window per call.  A window is small,
+a video is not: the net sees every frame twice (windows overlap 2x), about
+1.6 GFLOP per source frame, roughly three times the arithmetic of the
+ViT-B/32 embedder per second of video.  ``TransNetV2(backend="native")``
+therefore runs the conv trunk on the hand-written bf16 kernels
+(models/transnetv2_native.py, DESIGN.md "TransNetV2 native trunk"); the
+heads stay on torch f32.  Published weights
 (Sn4kehead/TransNetV2) are unavailable offline; the stand-in is the
 name-seeded deterministic generator below (same convention as
 clip_weights.py).
@@ -177,6 +183,13 @@ class _TransNetV2(nn.Module):
         for block in self.SDDCNN:
             x = block(x)
             feats.append(x)
+        return self.heads(inputs, feats)
+
+    @torch.no_grad()
+    def heads(self, inputs: torch.Tensor, feats: list[torch.Tensor]) -> torch.Tensor:
+        """Everything after the trunk: the u8 windows and the three pooled
+        stack outputs, f32 (B,C,T,h,w), -> (B,T,1) prob."""
+        x = feats[-1]
         x = x.permute(0, 2, 3, 4, 1).reshape(x.shape[0], x.shape[2], -1)
         x = torch.cat([self.frame_sim_layer(feats), x], dim=2)
         x = torch.cat([self.color_hist_layer(inputs), x], dim=2)
@@ -215,9 +228,14 @@ _TRANSNETV2_MODEL_ID = "Sn4kehead/TransNetV2"
 class TransNetV2(ModelInterface):
     """ModelInterface wrapper (reference transnetv2.py:530-600 surface)."""
 
-    def __init__(self) -> None:
+    def __init__(self, backend: str = "torch") -> None:
         super().__init__()
+        if backend not in ("torch", "native"):
+            msg = f"backend must be 'torch' or 'native', got {backend!r}"
+            raise ValueError(msg)
+        self.backend = backend
         self._model: _TransNetV2 | None = None
+        self._trunk = None
 
     @property
     def conda_env_name(self) -> str:
@@ -233,8 +251,23 @@ class TransNetV2(ModelInterface):
         self._model.eval()
         if torch.cuda.is_available():
             self._model.cuda()
+        if self.backend == "native":
+            # no fallback: without the library or a device this raises
+            from cosmos_curate_amd.models.transnetv2_native import NativeTrunk
+
+            self._trunk = NativeTrunk(self._model.state_dict())
 
     def __call__(self, inputs: torch.Tensor) -> torch.Tensor:
         assert self._model is not None, "setup() not called"
         with torch.no_grad():
-            return self._model(inputs)
+            if self._trunk is None:
+                return self._model(inputs)
+            assert inputs.dtype == torch.uint8 and tuple(inputs.shape[2:]) == (27, 48, 3)
+            feats = [f.float().permute(0, 4, 1, 2, 3) for f in self._trunk(inputs)]
+            # the heads run one window at a time whatever the batch: a torch
+            # GEMM may pick another kernel for another batch size, and a
+            # window's prediction must not depend on its neighbours
+            return torch.cat([
+                self._model.heads(inputs[b:b + 1], [f[b:b + 1] for f in feats])
+                for b in range(inputs.shape[0])
+            ])

@@ -9,7 +9,8 @@ video decoded to (N,27,48,3) u8).
 
 MI355X route: the tiny-res full-video decode reuses the fused NV12->RGB +
 bilinear resize kernel at a 48x27 target; the
-3D-conv net runs on torch-rocm (row 10).  Postprocess parity vs
+3D-conv net runs on torch-rocm (row 10) or, with ``backend="native"``, its
+conv trunk on the bf16 kernels of csrc/cc_conv.hip.  Postprocess parity vs
 oracle/transnet_post.py is exact; network parity vs the reference
 implementation is pinned by tests/golden/transnetv2_golden.npz.
 """
@@ -63,6 +64,36 @@ def _get_predictions(
             t = t.cuda()
         one_hot = model(t.unsqueeze(0))
         preds.append(one_hot[0, 25:75])
+    stacked = torch.cat(preds, 0)[: len(frames)]
+    return (stacked > threshold).to(torch.uint8).cpu().numpy()
+
+
+_NATIVE_MAX_WINDOWS = 16  # windows per forward of the native route
+
+
+def _get_predictions_native(
+    model, frames: npt.NDArray[np.uint8], threshold: float
+) -> npt.NDArray[np.uint8]:
+    """``_get_predictions`` for ``TransNetV2(backend="native")``: the frames
+    go to the device once, the windows of ``_get_batches`` are gathered there
+    (``transnetv2_native.window_indices``), and windows of equal length run
+    up to ``_NATIVE_MAX_WINDOWS`` per forward.  Same windows, same kept
+    frames (25..74 of each), same threshold."""
+    from cosmos_curate_amd.models.transnetv2_native import window_indices
+
+    dev = torch.from_numpy(np.ascontiguousarray(frames)).cuda()
+    windows = window_indices(len(frames))
+    preds = []
+    start = 0
+    while start < len(windows):
+        stop = start + 1
+        while (stop < len(windows) and stop - start < _NATIVE_MAX_WINDOWS
+               and len(windows[stop]) == len(windows[start])):
+            stop += 1
+        idx = torch.stack(windows[start:stop]).to(dev.device)
+        one_hot = model(dev[idx])
+        preds.append(one_hot[:, 25:75].reshape(-1, one_hot.shape[-1]))
+        start = stop
     stacked = torch.cat(preds, 0)[: len(frames)]
     return (stacked > threshold).to(torch.uint8).cpu().numpy()
 
@@ -206,6 +237,7 @@ class TransNetV2ClipExtractionStage(CuratorStage):
         limit_clips: int = 0,
         verbose: bool = False,
         log_stats: bool = False,
+        backend: str = "torch",
     ) -> None:
         self._timer = StageTimer(self)
         self.threshold = threshold
@@ -222,7 +254,10 @@ class TransNetV2ClipExtractionStage(CuratorStage):
         self._limit_clips = limit_clips
         self._verbose = verbose
         self._log_stats = log_stats
-        self._model = transnetv2.TransNetV2()
+        # "torch": f32 nn.Conv3d, one window per call; "native": the bf16
+        # conv trunk of models/transnetv2_native.py, windows built on device
+        self.backend = backend
+        self._model = transnetv2.TransNetV2(backend=backend)
 
     @property
     def resources(self) -> CuratorStageResource:
@@ -254,7 +289,8 @@ class TransNetV2ClipExtractionStage(CuratorStage):
                 if tuple(frames.shape[1:4]) != (27, 48, 3):
                     msg = f"Expected frames of shape 27x48x3, got {frames.shape[1:4]}."
                     raise ValueError(msg)
-                predictions = _get_predictions(self._model, frames, self.threshold)
+                get = _get_predictions_native if self.backend == "native" else _get_predictions
+                predictions = get(self._model, frames, self.threshold)
                 scenes = _get_scenes(predictions, entire_scene_as_clip=self.entire_scene_as_clip)
                 filtered = _get_filtered_scenes(
                     scenes,

@@ -154,6 +154,7 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
                 threshold=args.transnetv2_threshold,
                 limit_clips=args.limit_clips,
                 log_stats=True,
+                backend=args.transnetv2_backend,
             )
         )
     else:
@@ -261,6 +262,11 @@ def _setup_parser(parser: argparse.ArgumentParser) -> None:
                         dest="fixed_stride_min_clip_length",
                         type=float, default=10.0)
     parser.add_argument("--transnetv2-threshold", type=float, default=0.4)
+    parser.add_argument(
+        "--transnetv2-backend", default="torch", choices=["torch", "native"],
+        help="torch: f32 nn.Conv3d per window; native: the bf16 conv trunk "
+             "kernels, up to 16 windows per forward",
+    )
     parser.add_argument("--limit", type=int, default=0)
     parser.add_argument("--limit-clips", type=int, default=0)
     parser.add_argument("--num-clips-per-chunk", type=int, default=32)

@@ -543,6 +543,49 @@ int cc_embed_assemble_ln(const void* tok, const void* cls, const void* pos,
                          int64_t n_frames, int64_t tokens, int64_t H,
                          float eps, uint64_t stream);
 
+/* ---- TransNetV2 trunk: bf16 (2+1)D convolutions (csrc/cc_conv.hip) ----
+ * Replace the f32 nn.Conv3d pairs of the shot detector's DDCNN blocks
+ * (models/transnetv2.py:279-347, :224-277, :152-222).  Activations are bf16
+ * channels-last [frames, H, W, C], accumulation is f32 in a fixed order with
+ * no atomics: bit-identical from run to run and for any batch.  All
+ * pointers 16-byte aligned (the u8 input aside).  Every entry checks its
+ * arguments on the host before any launch, so a rejected call touches no
+ * device: CC_ERR_INVALID on null or misaligned pointers and non-positive
+ * sizes, CC_ERR_UNSUPPORTED on a channel count outside the stated set or a
+ * grid past 2^31-1 workgroups.
+ *
+ * cc_conv3x3_bf16: y[n,h,w,co] = sum_{dy,dx,ci} x[n,h+dy,w+dx,ci] *
+ * w[co,dy,dx,ci], zero padding 1, no bias, no activation.  x [frames,H,W,
+ * Cin], w [Cout][3][3][Cin], y [frames,H,W,Cout]; Cin 64, 128 or 256, Cout a
+ * multiple of 16 up to 512 (the four dilation branches of a block share
+ * their input, so one launch computes all of them: Cout = 8F).  Implicit
+ * GEMM on the 16x16x32 bf16 MFMA over the flattened (frame, pixel) index.
+ * cc_conv3x3_u8: the same conv for the 3-channel first layer: x u8
+ * [frames,H,W,3] taken as bf16(x/255) (f32 division, one rounding), w bf16
+ * [Cout][3][3][3].  A plain FMA kernel (K = 27).  Both timed as "conv3x3".
+ *
+ * cc_tconv3_bf16: the four dilated 3-tap temporal convs of a block with its
+ * folded BatchNorm.  x [B,T,HW,8F], w [4][F][3][2F], bias f32 [4F],
+ * y [B,T,HW,4F]; branch b reads channels [b*2F, (b+1)*2F) at frames t-2^b,
+ * t, t+2^b of the same window (zero padding at each window's ends, never
+ * across windows) and writes channels [b*F, (b+1)*F):
+ *   y = bf16(relu(acc + bias) + shortcut)
+ * shortcut bf16 [B,T,HW,4F] or NULL (the stack tail relu(x) + shortcut).
+ * F 16, 32 or 64; T >= 1.  Timed as "tconv3".
+ *
+ * cc_avgpool2x2_bf16: AvgPool3d((1,2,2)): [frames,H,W,C] -> [frames,H/2,
+ * W/2,C], odd sizes floored, f32 sum and one rounding; C % 8 == 0, H and W
+ * at least 2.  Timed as "avgpool". */
+int cc_conv3x3_bf16(const void* x, const void* w, void* y, int64_t frames,
+                    int H, int W, int Cin, int Cout, uint64_t stream);
+int cc_conv3x3_u8(const void* x, const void* w, void* y, int64_t frames, int H,
+                  int W, int Cout, uint64_t stream);
+int cc_tconv3_bf16(const void* x, const void* w, const float* bias,
+                   const void* shortcut, void* y, int64_t B, int T, int HW,
+                   int F, uint64_t stream);
+int cc_avgpool2x2_bf16(const void* x, void* y, int64_t frames, int H, int W,
+                       int C, uint64_t stream);
+
 /* ---- semantic dedup -------------------------------------------------
  * Strict-upper-triangular max-cosine scan (SemDedupActor.dedup,
  * pipelines/video/dedup/dedup_actor.py:315-460): for each row j of the
