@@ -12,6 +12,8 @@ Per-file flags:
 - cc_motion.hip: integer arithmetic only; no floating-point flags matter.
 - cc_conv.hip: default contraction (MFMA, and an FMA first layer whose
   tolerance is the f32 accumulation bound, not bit-exactness).
+- cc_tnheads.hip: -ffp-contract=off — the histogram head is bit-equal to its
+  numpy restatement, and the f32 chains say fmaf where they mean it.
 """
 
 from __future__ import annotations
@@ -38,6 +40,7 @@ SOURCES: list[tuple[str, list[str]]] = [
     ("cc_attn.hip", [ARCH]),
     ("cc_motion.hip", [ARCH]),
     ("cc_conv.hip", [ARCH]),
+    ("cc_tnheads.hip", [ARCH, "-ffp-contract=off"]),
 ]
 
 

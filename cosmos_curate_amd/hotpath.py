@@ -198,6 +198,21 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.cc_avgpool2x2_bf16.argtypes = [
         c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int, c.c_int,
         c.c_uint64]
+    lib.cc_tn_hist512_u8.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_uint64]
+    lib.cc_tn_framesim_embed.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int,
+        c.c_int, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_void_p,
+        c.c_void_p, c.c_int64, c.c_int, c.c_uint64]
+    lib.cc_tn_simband_fc.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int,
+        c.c_int, c.c_int, c.c_int, c.c_uint64]
+    lib.cc_tn_fc1_relu.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+        c.c_void_p, c.c_int64, c.c_int, c.c_int, c.c_int, c.c_uint64]
+    lib.cc_tn_cls_sigmoid.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_float, c.c_void_p, c.c_int64, c.c_int,
+        c.c_uint64]
 
     lib.cc_timing_enable.argtypes = [c.c_int]
     lib.cc_timing_report.argtypes = [
@@ -512,6 +527,58 @@ def avgpool2x2_bf16(x_ptr: int, y_ptr: int, frames: int, h: int, w: int,
     """2x2 average pool of bf16 channels-last frames, odd sizes floored
     (cc_avgpool2x2_bf16): [frames,h,w,c] -> [frames,h//2,w//2,c]."""
     check(load().cc_avgpool2x2_bf16(x_ptr, y_ptr, frames, h, w, c, stream))
+
+
+def tn_hist512_u8(frames_ptr: int, out_ptr: int, frames: int, pixels: int,
+                  stream: int) -> None:
+    """L2-normalised 512-bin RGB histograms (cc_tn_hist512_u8): u8
+    [frames,pixels,3] -> f32 [frames,512]; at most 4096 pixels a frame."""
+    check(load().cc_tn_hist512_u8(frames_ptr or None, out_ptr or None, frames,
+                                  pixels, stream))
+
+
+def tn_framesim_embed(maps: list[tuple[int, int, int]], proj_wt_ptr: int,
+                      proj_b_ptr: int, out_ptr: int, frames: int, out_dim: int,
+                      stream: int) -> None:
+    """Spatial means of up to three bf16 channels-last maps, projection and
+    L2 normalisation (cc_tn_framesim_embed).  ``maps`` holds (pointer, hw,
+    channels) per map [frames,hw,channels]; weights f32 [sum channels][128]
+    (transposed), out f32 [frames,128]."""
+    n = len(maps)
+    ptrs, hws, cs = ([m[i] for m in maps] + [0] * (3 - n) for i in range(3))
+    check(load().cc_tn_framesim_embed(
+        *(p or None for p in ptrs[:3]), *hws[:3], *cs[:3], n, proj_wt_ptr or None,
+        proj_b_ptr or None, out_ptr or None, frames, out_dim, stream))
+
+
+def tn_simband_fc(x_ptr: int, fc_wt_ptr: int, fc_b_ptr: int, out_ptr: int,
+                  b: int, t: int, d: int, ldo: int, col: int, stream: int) -> None:
+    """The 101-wide similarity band of every frame of x f32 [b,t,d] (d 128 or
+    512), Linear(101,128) with weights f32 [101][128] (transposed) and relu
+    (cc_tn_simband_fc), into columns [col, col+128) of out f32 [b*t,ldo]."""
+    check(load().cc_tn_simband_fc(x_ptr or None, fc_wt_ptr or None,
+                                  fc_b_ptr or None, out_ptr or None, b, t, d,
+                                  ldo, col, stream))
+
+
+def tn_fc1_relu(hd_ptr: int, feat_ptr: int, w_hi_ptr: int, w_lo_ptr: int,
+                bias_ptr: int, y_ptr: int, m: int, kh: int, kf: int, n: int,
+                stream: int) -> None:
+    """relu(bias + [hd | feat] . w^T) with split-bf16 operands
+    (cc_tn_fc1_relu): hd f32 [m,kh], feat bf16 [m,kf], w_hi and w_lo bf16
+    [n][kh+kf], bias f32 [n], y f32 [m,n]."""
+    check(load().cc_tn_fc1_relu(hd_ptr or None, feat_ptr or None,
+                                w_hi_ptr or None, w_lo_ptr or None,
+                                bias_ptr or None, y_ptr or None, m, kh, kf, n,
+                                stream))
+
+
+def tn_cls_sigmoid(y_ptr: int, w_ptr: int, b: float, p_ptr: int, m: int, n: int,
+                   stream: int) -> None:
+    """sigmoid(b + y . w) per row (cc_tn_cls_sigmoid): y f32 [m,n], w f32
+    [n], p f32 [m]."""
+    check(load().cc_tn_cls_sigmoid(y_ptr or None, w_ptr or None, b,
+                                   p_ptr or None, m, n, stream))
 
 
 def gemm_plan(

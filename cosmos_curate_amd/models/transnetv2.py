@@ -17,7 +17,8 @@ a video is not: the net sees every frame twice (windows overlap 2x), about
 ViT-B/32 embedder per second of video.  ``TransNetV2(backend="native")``
 therefore runs the conv trunk on the hand-written bf16 kernels
 (models/transnetv2_native.py, DESIGN.md "TransNetV2 native trunk"); the
-heads stay on torch f32.  Published weights
+heads stay on torch f32 unless ``heads="native"`` puts them on the kernels
+of csrc/cc_tnheads.hip as well.  Published weights
 (Sn4kehead/TransNetV2) are unavailable offline; the stand-in is the
 name-seeded deterministic generator below (same convention as
 clip_weights.py).
@@ -228,14 +229,22 @@ _TRANSNETV2_MODEL_ID = "Sn4kehead/TransNetV2"
 class TransNetV2(ModelInterface):
     """ModelInterface wrapper (reference transnetv2.py:530-600 surface)."""
 
-    def __init__(self, backend: str = "torch") -> None:
+    def __init__(self, backend: str = "torch", heads: str = "torch") -> None:
         super().__init__()
         if backend not in ("torch", "native"):
             msg = f"backend must be 'torch' or 'native', got {backend!r}"
             raise ValueError(msg)
+        if heads not in ("torch", "native"):
+            msg = f"heads must be 'torch' or 'native', got {heads!r}"
+            raise ValueError(msg)
+        if heads == "native" and backend != "native":
+            msg = "heads='native' reads the native trunk's features: it needs backend='native'"
+            raise ValueError(msg)
         self.backend = backend
+        self.heads = heads
         self._model: _TransNetV2 | None = None
         self._trunk = None
+        self._heads = None
 
     @property
     def conda_env_name(self) -> str:
@@ -256,6 +265,10 @@ class TransNetV2(ModelInterface):
             from cosmos_curate_amd.models.transnetv2_native import NativeTrunk
 
             self._trunk = NativeTrunk(self._model.state_dict())
+            if self.heads == "native":
+                from cosmos_curate_amd.models.transnetv2_native import NativeHeads
+
+                self._heads = NativeHeads(self._model.state_dict())
 
     def __call__(self, inputs: torch.Tensor) -> torch.Tensor:
         assert self._model is not None, "setup() not called"
@@ -263,6 +276,9 @@ class TransNetV2(ModelInterface):
             if self._trunk is None:
                 return self._model(inputs)
             assert inputs.dtype == torch.uint8 and tuple(inputs.shape[2:]) == (27, 48, 3)
+            if self._heads is not None:
+                # fixed summation order whatever the batch: one pass for all windows
+                return self._heads(inputs, self._trunk(inputs))
             feats = [f.float().permute(0, 4, 1, 2, 3) for f in self._trunk(inputs)]
             # the heads run one window at a time whatever the batch: a torch
             # GEMM may pick another kernel for another batch size, and a

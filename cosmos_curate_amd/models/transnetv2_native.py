@@ -16,9 +16,16 @@ transnetv2.py:152-347), repacked for channels-last bf16:
 ``pack_trunk`` works from any state dict of ``_TransNetV2`` on the CPU and
 knows nothing of where the weights came from; ``NativeTrunk`` uploads the
 packed tensors and runs ``(B, T, 27, 48, 3)`` u8 windows to the three pooled
-stack outputs, channels-last ``(B, T, h, w, 4F)`` bf16.  The heads stay on
-torch (``_TransNetV2.heads``).  No fallback: a missing library or kernel
-raises.
+stack outputs, channels-last ``(B, T, h, w, 4F)`` bf16.  No fallback: a
+missing library or kernel raises.
+
+The heads stay on torch (``_TransNetV2.heads``) unless asked for:
+``pack_heads`` / ``NativeHeads`` are the same pair for everything after the
+trunk, on the kernels of csrc/cc_tnheads.hip (DESIGN.md "TransNetV2 native
+heads"): colour histograms, the frame-similarity embedding, the two
+101-frame similarity bands with their ``Linear(101, 128)``, ``fc1`` with its
+weight split into a bf16 hi and lo part, and the classifier.  They sum in a
+fixed order, so all windows of a forward go through them in one pass.
 """
 
 from __future__ import annotations
@@ -86,6 +93,73 @@ def pack_trunk(state_dict: dict[str, torch.Tensor]) -> list[list[PackedBlock]]:
     if not stacks:
         raise ValueError("state dict holds no SDDCNN trunk")
     return stacks
+
+
+_LOOKUP = 101  # lookup window of both similarity heads
+
+
+@dataclass
+class PackedHeads:
+    """Everything after the trunk, on the CPU, in the kernels' layouts (f32
+    unless noted)."""
+
+    proj_wt: torch.Tensor     # [sum 4F, 128], frame_sim_layer.projection.weight^T
+    proj_b: torch.Tensor      # [128]
+    sim_fc_wt: torch.Tensor   # [101, 128], frame_sim_layer.fc.weight^T
+    sim_fc_b: torch.Tensor    # [128]
+    hist_fc_wt: torch.Tensor  # [101, 128], color_hist_layer.fc.weight^T
+    hist_fc_b: torch.Tensor   # [128]
+    fc1_hi: torch.Tensor      # bf16 [N, 256 + KF]: bf16(w)
+    fc1_lo: torch.Tensor      # bf16 [N, 256 + KF]: bf16(w - float(fc1_hi))
+    fc1_b: torch.Tensor       # [N]
+    cls_w: torch.Tensor       # [N]
+    cls_b: float
+
+
+def pack_heads(state_dict: dict[str, torch.Tensor]) -> PackedHeads:
+    """The head entries of a ``_TransNetV2`` state dict as ``PackedHeads``.
+    ``fc1.weight``'s columns are already in the kernels' order: colour head
+    (128), frame-similarity head (128), then stack 3's pooled output
+    flattened ``(h, w, C)``."""
+    names = ("frame_sim_layer.projection.weight", "frame_sim_layer.projection.bias",
+             "frame_sim_layer.fc.weight", "frame_sim_layer.fc.bias",
+             "color_hist_layer.fc.weight", "color_hist_layer.fc.bias",
+             "fc1.weight", "fc1.bias", "cls_layer1.weight", "cls_layer1.bias")
+    missing = [n for n in names if n not in state_dict]
+    if missing:
+        raise ValueError(f"state dict holds no heads: {', '.join(missing)} missing")
+    proj_w, proj_b, sim_w, sim_b, hist_w, hist_b, fc1_w, fc1_b, cls_w, cls_b = (
+        state_dict[n].detach().float().cpu() for n in names)
+
+    def want(name: str, t: torch.Tensor, *shape: int | None) -> None:
+        if t.ndim != len(shape) or any(s is not None and s != d
+                                       for s, d in zip(shape, t.shape)):
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected "
+                             f"{tuple('any' if s is None else s for s in shape)}")
+
+    want("frame_sim_layer.projection.weight", proj_w, 128, None)
+    want("frame_sim_layer.projection.bias", proj_b, 128)
+    for n, w, b in (("frame_sim_layer", sim_w, sim_b), ("color_hist_layer", hist_w, hist_b)):
+        want(n + ".fc.weight", w, 128, _LOOKUP)
+        want(n + ".fc.bias", b, 128)
+    want("fc1.weight", fc1_w, None, None)
+    n_out, k = fc1_w.shape
+    want("fc1.bias", fc1_b, n_out)
+    want("cls_layer1.weight", cls_w, 1, n_out)
+    want("cls_layer1.bias", cls_b, 1)
+    if proj_w.shape[1] > 512:
+        raise ValueError("the projection reads at most 512 channel means")
+    if n_out % 16 != 0 or k <= 256 or (k - 256) % 32 != 0:
+        raise ValueError(f"fc1.weight {tuple(fc1_w.shape)}: outputs must be a multiple "
+                         "of 16, inputs 256 plus a multiple of 32")
+    hi = fc1_w.to(torch.bfloat16)
+    lo = (fc1_w - hi.float()).to(torch.bfloat16)
+    return PackedHeads(
+        proj_w.t().contiguous(), proj_b.contiguous(),
+        sim_w.t().contiguous(), sim_b.contiguous(),
+        hist_w.t().contiguous(), hist_b.contiguous(),
+        hi.contiguous(), lo.contiguous(), fc1_b.contiguous(),
+        cls_w[0].contiguous(), float(cls_b[0]))
 
 
 def window_indices(total: int) -> list[torch.Tensor]:
@@ -163,3 +237,68 @@ class NativeTrunk:
                 feats.append(p.view(b, t, h, w, -1))
                 x = p
         return feats
+
+
+class NativeHeads:
+    """The packed heads on one device: ``(frames_u8 (B,T,H,W,3), feats from
+    NativeTrunk) -> (B,T,1)`` f32 probabilities, six launches and no torch
+    arithmetic between them."""
+
+    def __init__(self, state_dict: dict[str, torch.Tensor],
+                 device: torch.device | str = "cuda") -> None:
+        hotpath.require_gpu()
+        self.device = torch.device(device)
+        p = pack_heads(state_dict)
+        self.cls_b = p.cls_b
+        (self.proj_wt, self.proj_b, self.sim_fc_wt, self.sim_fc_b, self.hist_fc_wt,
+         self.hist_fc_b, self.fc1_hi, self.fc1_lo, self.fc1_b, self.cls_w) = (
+            t.to(self.device) for t in (
+                p.proj_wt, p.proj_b, p.sim_fc_wt, p.sim_fc_b, p.hist_fc_wt,
+                p.hist_fc_b, p.fc1_hi, p.fc1_lo, p.fc1_b, p.cls_w))
+
+    @torch.no_grad()
+    def __call__(self, frames_u8: torch.Tensor, feats: list[torch.Tensor]) -> torch.Tensor:
+        if (frames_u8.dtype != torch.uint8 or frames_u8.ndim != 5
+                or frames_u8.shape[-1] != 3 or not frames_u8.is_cuda):
+            raise ValueError("frames must be a (B, T, H, W, 3) uint8 device tensor")
+        b, t, h, w, _ = frames_u8.shape
+        n = b * t
+        for f in feats:
+            if (f.dtype != torch.bfloat16 or f.ndim != 5 or tuple(f.shape[:2]) != (b, t)
+                    or not f.is_cuda or not f.is_contiguous()):
+                raise ValueError("features must be contiguous (B, T, h, w, C) bf16 "
+                                 "device tensors of the frames' windows")
+        if sum(f.shape[-1] for f in feats) != self.proj_wt.shape[0]:
+            raise ValueError("the features' channels do not match the projection")
+        n_out, k = self.fc1_hi.shape
+        kf = feats[-1][0, 0].numel()
+        if k != 256 + kf:
+            raise ValueError(f"fc1 reads {k} inputs, the heads give 256 + {kf}")
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+
+            def new(*shape):
+                return torch.empty(shape, dtype=torch.float32, device=self.device)
+
+            x = frames_u8.contiguous()
+            hist, emb, hd, y, prob = new(n, 512), new(n, 128), new(n, 256), new(n, n_out), new(n)
+            hotpath.tn_hist512_u8(x.data_ptr(), hist.data_ptr(), n, h * w, stream)
+            hotpath.tn_framesim_embed(
+                [(f.data_ptr(), f.shape[2] * f.shape[3], f.shape[4]) for f in feats],
+                self.proj_wt.data_ptr(), self.proj_b.data_ptr(), emb.data_ptr(), n, 128,
+                stream)
+            # _TransNetV2.heads' concatenation: colour head, similarity head, features
+            hotpath.tn_simband_fc(hist.data_ptr(), self.hist_fc_wt.data_ptr(),
+                                  self.hist_fc_b.data_ptr(), hd.data_ptr(), b, t, 512,
+                                  256, 0, stream)
+            hotpath.tn_simband_fc(emb.data_ptr(), self.sim_fc_wt.data_ptr(),
+                                  self.sim_fc_b.data_ptr(), hd.data_ptr(), b, t, 128,
+                                  256, 128, stream)
+            # stack 3's pooled output is (h, w, C)-contiguous per frame: the
+            # flatten order of the heads, read in place
+            hotpath.tn_fc1_relu(hd.data_ptr(), feats[-1].data_ptr(), self.fc1_hi.data_ptr(),
+                                self.fc1_lo.data_ptr(), self.fc1_b.data_ptr(), y.data_ptr(),
+                                n, 256, kf, n_out, stream)
+            hotpath.tn_cls_sigmoid(y.data_ptr(), self.cls_w.data_ptr(), self.cls_b,
+                                   prob.data_ptr(), n, n_out, stream)
+        return prob.view(b, t, 1)

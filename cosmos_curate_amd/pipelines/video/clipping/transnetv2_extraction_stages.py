@@ -10,7 +10,8 @@ video decoded to (N,27,48,3) u8).
 MI355X route: the tiny-res full-video decode reuses the fused NV12->RGB +
 bilinear resize kernel at a 48x27 target; the
 3D-conv net runs on torch-rocm (row 10) or, with ``backend="native"``, its
-conv trunk on the bf16 kernels of csrc/cc_conv.hip.  Postprocess parity vs
+conv trunk on the bf16 kernels of csrc/cc_conv.hip and, with
+``heads="native"``, the heads on csrc/cc_tnheads.hip.  Postprocess parity vs
 oracle/transnet_post.py is exact; network parity vs the reference
 implementation is pinned by tests/golden/transnetv2_golden.npz.
 """
@@ -238,6 +239,7 @@ class TransNetV2ClipExtractionStage(CuratorStage):
         verbose: bool = False,
         log_stats: bool = False,
         backend: str = "torch",
+        heads: str = "torch",
     ) -> None:
         self._timer = StageTimer(self)
         self.threshold = threshold
@@ -257,7 +259,10 @@ class TransNetV2ClipExtractionStage(CuratorStage):
         # "torch": f32 nn.Conv3d, one window per call; "native": the bf16
         # conv trunk of models/transnetv2_native.py, windows built on device
         self.backend = backend
-        self._model = transnetv2.TransNetV2(backend=backend)
+        # "native" (with backend="native" only): the heads on the kernels of
+        # csrc/cc_tnheads.hip too, all windows of a forward in one pass
+        self.heads = heads
+        self._model = transnetv2.TransNetV2(backend=backend, heads=heads)
 
     @property
     def resources(self) -> CuratorStageResource:

@@ -134,6 +134,10 @@ def build_input_data(args: argparse.Namespace) -> list[SplitPipeTask]:
 
 def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorStageSpec]:
     """Ordered stage list (splitting_pipeline.py:333-885)."""
+    if (getattr(args, "transnetv2_heads", "torch") == "native"
+            and args.transnetv2_backend != "native"):
+        msg = "--transnetv2-heads native requires --transnetv2-backend native"
+        raise ValueError(msg)
     stages: list[CuratorStage | CuratorStageSpec] = [
         VideoDownloader(args.input_video_path, verbose=args.verbose, log_stats=True),
     ]
@@ -155,6 +159,7 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
                 limit_clips=args.limit_clips,
                 log_stats=True,
                 backend=args.transnetv2_backend,
+                heads=getattr(args, "transnetv2_heads", "torch"),
             )
         )
     else:
@@ -267,6 +272,12 @@ def _setup_parser(parser: argparse.ArgumentParser) -> None:
         help="torch: f32 nn.Conv3d per window; native: the bf16 conv trunk "
              "kernels, up to 16 windows per forward",
     )
+    parser.add_argument(
+        "--transnetv2-heads", default="torch", choices=["torch", "native"],
+        help="torch: the f32 heads, one window at a time; native: the head "
+             "kernels, all windows of a forward in one pass (needs "
+             "--transnetv2-backend native)",
+    )
     parser.add_argument("--limit", type=int, default=0)
     parser.add_argument("--limit-clips", type=int, default=0)
     parser.add_argument("--num-clips-per-chunk", type=int, default=32)
@@ -352,6 +363,8 @@ def split(args: argparse.Namespace, runner: RunnerInterface | None = None) -> di
                 line += f" hdr={hdr} hdr_peak_nits={inner._hdr_peak_nits:g}"
             if resize != "cubic":
                 line += f" resize={resize}"
+            if getattr(inner, "heads", "torch") != "torch":
+                line += f" heads={inner.heads}"
             print(line)
         return {"dry_run": True, "num_input_videos": len(input_tasks),
                 "num_stages": len(stages)}

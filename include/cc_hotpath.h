@@ -586,6 +586,72 @@ int cc_tconv3_bf16(const void* x, const void* w, const float* bias,
 int cc_avgpool2x2_bf16(const void* x, void* y, int64_t frames, int H, int W,
                        int C, uint64_t stream);
 
+/* ---- TransNetV2 heads (csrc/cc_tnheads.hip) ----------------------------
+ * Everything after the trunk (models/transnetv2.py: ColorHistograms,
+ * FrameSimilarity, fc1, cls_layer1), for all windows of a forward in one
+ * pass.  Every sum is f32 in an order fixed by one window's shape: no float
+ * atomics, no split-K, no workgroup across two windows, so results are
+ * bit-identical from run to run and for any B, and a window never reads
+ * another window's frames.  Any T >= 1.  Every entry checks its arguments on
+ * the host before any launch, so a rejected call touches no device:
+ * CC_ERR_INVALID on null or misaligned pointers (16 bytes; the u8 frames and
+ * the f32 probabilities aside) and non-positive sizes, CC_ERR_UNSUPPORTED on
+ * sizes outside the stated set.
+ *
+ * cc_tn_hist512_u8: frames_u8 [frames, pixels, 3] -> out f32 [frames, 512].
+ * bin = (r>>5)<<6 | (g>>5)<<3 | (b>>5); integer counts c (LDS integer
+ * atomics: order-free, exact); out = float(c) / fmaxf(sqrtf(float(sum c^2)),
+ * 1e-12f).  pixels <= 4096 keeps sum c^2 <= 2^24 exact in f32, and with
+ * correctly rounded sqrtf and division the result is bit-equal to the numpy
+ * restatement.  One workgroup per frame.  Timed as "tn_hist512".
+ *
+ * cc_tn_framesim_embed: n_maps (1..3) pooled stack outputs x_i bf16
+ * channels-last [frames, hw_i, c_i] -> out f32 [frames, 128].  Per frame the
+ * spatial mean of every channel (f32 sum in ascending pixel order, then
+ * / hw_i), the means concatenated in map order (c_i % 8 == 0, sum c_i <=
+ * 512), then e[o] = chain over k ascending of fmaf(mean[k], proj_wt[k][o]) + proj_b[o]
+ * with proj_wt f32 [sum c_i][128] (the Linear's weight transposed), then
+ * out = e / fmaxf(sqrtf(sum e^2), 1e-12f).  out_dim must be 128.  One
+ * workgroup per frame.  Timed as "tn_framesim_embed".
+ *
+ * cc_tn_simband_fc: x f32 [B, T, D], D 128 or 512.  s[j] = <x[b,t],
+ * x[b,t+j-50]> for j = 0..100, 0 where the partner lies outside [0, T);
+ * y[o] = relu(fc_b[o] + chain over j ascending of fmaf(fc_wt[j][o], s[j]))
+ * for the 128 outputs, fc_wt f32 [101][128] (the Linear's weight
+ * transposed; staged in LDS).  Written to out f32 [B*T, ldo] at columns
+ * [col, col+128).  Only the band is computed, never the T x T matrix.  A
+ * workgroup takes two consecutive frames of one window.  Timed as
+ * "tn_simband_fc".
+ *
+ * cc_tn_fc1_relu: y f32 [M, N] = relu(bias + [hd | feat] . w^T) with hd f32
+ * [M, KH], feat bf16 [M, KF], w_hi and w_lo bf16 [N][KH+KF] (w_hi = bf16(w),
+ * w_lo = bf16(w - float(w_hi))), bias f32 [N].  On the 16x16x32 bf16 MFMA
+ * into one f32 accumulator in this order: feat.w_hi, feat.w_lo, hd_hi.w_hi,
+ * hd_hi.w_lo, hd_lo.w_hi, with hd_hi = bf16(hd), hd_lo = bf16(hd -
+ * float(hd_hi)) formed in registers.  KH % 32 == 0, KF % 32 == 0,
+ * N % 16 == 0.  One tile shape (a wave owns 32 rows x 32 outputs) for every
+ * M; fragments straight from global memory, row tails guarded.  Timed as
+ * "tn_fc1_relu".
+ *
+ * cc_tn_cls_sigmoid: p[m] = 1 / (1 + expf(-(b + sum_n w[n] * y[m,n]))), y f32
+ * [M, N], w f32 [N], p f32 [M]; one wave per row, lane l chains n = l, l+64,
+ * ... ascending, then a fixed butterfly.  Timed as "tn_cls_sigmoid". */
+int cc_tn_hist512_u8(const void* frames_u8, void* out, int64_t frames,
+                     int pixels, uint64_t stream);
+int cc_tn_framesim_embed(const void* x0, const void* x1, const void* x2,
+                         int hw0, int hw1, int hw2, int c0, int c1, int c2,
+                         int n_maps, const float* proj_wt, const float* proj_b,
+                         void* out, int64_t frames, int out_dim,
+                         uint64_t stream);
+int cc_tn_simband_fc(const float* x, const float* fc_wt, const float* fc_b,
+                     void* out, int64_t B, int T, int D, int ldo, int col,
+                     uint64_t stream);
+int cc_tn_fc1_relu(const float* hd, const void* feat, const void* w_hi,
+                   const void* w_lo, const float* bias, void* y, int64_t M,
+                   int KH, int KF, int N, uint64_t stream);
+int cc_tn_cls_sigmoid(const float* y, const float* w, float b, void* p,
+                      int64_t M, int N, uint64_t stream);
+
 /* ---- semantic dedup -------------------------------------------------
  * Strict-upper-triangular max-cosine scan (SemDedupActor.dedup,
  * pipelines/video/dedup/dedup_actor.py:315-460): for each row j of the

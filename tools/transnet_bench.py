@@ -1,6 +1,7 @@
 """Time the TransNetV2 shot detector (stand-in weights) on one MI355X: the
-route the stage runs by default against a torch bf16 trunk and the native
-bf16 trunk, the legs alternating in one process.
+route the stage runs by default against a torch bf16 trunk, the native bf16
+trunk with torch heads and the native trunk with native heads, the legs
+alternating in one process.
 
     python tools/transnet_bench.py [--windows 1,8,16 --forwards 30
                                     --warmup 5 --video-frames 1600] [--out LOG]
@@ -12,15 +13,18 @@ page:
     call, W calls (what the stage does by default),
   - torch bf16 channels_last: the same trunk modules in bf16 and
     channels_last_3d, W windows in one forward, f32 heads on its features,
-  - native: ``TransNetV2(backend="native")``, W windows in one forward.
+  - native: ``TransNetV2(backend="native")``, W windows in one forward, the
+    torch heads one window at a time,
+  - native, native heads: ``TransNetV2(backend="native", heads="native")``,
+    trunk and heads for W windows in one pass.
 Device time from HIP events around each launch of a leg; median, min, max.
-Then the kernel-time split of a native forward from the library's own timers
-(cc_timing_*) and the trunk's achieved FLOP/s: 2*M*N*K over the six DDCNN
+Then the kernel-time split of a native forward (and of one with native heads)
+from the library's own timers (cc_timing_*) and the trunk's achieved FLOP/s: 2*M*N*K over the six DDCNN
 blocks (about 82 GFLOP per window) over that kernel time.
 
-Last, the stage's two routes end to end on one synthetic (N, 27, 48, 3)
+Last, the stage's three routes end to end on one synthetic (N, 27, 48, 3)
 video, host clock around ``_get_predictions`` / ``_get_predictions_native``
-(both end in a device-to-host copy), alternating, each twice.
+(all end in a device-to-host copy), alternating, each twice.
 
 Needs a GPU; there is no fallback.
 """
@@ -46,6 +50,8 @@ from cosmos_curate_amd.pipelines.video.clipping import (  # noqa: E402
 )
 
 TIMERS = ("conv3x3", "tconv3", "avgpool")
+HEAD_TIMERS = ("tn_hist512", "tn_framesim_embed", "tn_simband_fc", "tn_fc1_relu",
+               "tn_cls_sigmoid")
 
 
 def trunk_flop_per_frame() -> float:
@@ -98,7 +104,20 @@ def _summary(times: dict[str, np.ndarray], base: str, unit_count: float, unit: s
     return lines
 
 
-def bench_windows(torch_model, native_model, trunk16, nwin: int, warmup: int,
+def _kernel_split(fn, timers: tuple[str, ...], reps: int = 3) -> dict[str, tuple[float, int]]:
+    """Per-forward (ms, launches) of each timer over ``reps`` forwards."""
+    hotpath.timing_enable(True)  # also clears the totals
+    try:
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        total = {n: hotpath.timing_report(n) for n in timers}
+    finally:
+        hotpath.timing_enable(False)
+    return {n: (ms / reps, count // reps) for n, (ms, count) in total.items()}
+
+
+def bench_windows(torch_model, native_model, heads_model, trunk16, nwin: int, warmup: int,
                   forwards: int) -> list[str]:
     gen = torch.Generator().manual_seed(nwin)
     x = torch.randint(0, 256, (nwin, 100, 27, 48, 3), generator=gen, dtype=torch.uint8).cuda()
@@ -120,41 +139,55 @@ def bench_windows(torch_model, native_model, trunk16, nwin: int, warmup: int,
     def native():
         return native_model(x)
 
+    def native_heads():
+        return heads_model(x)
+
     legs = {"torch f32 per window": f32_per_window, "torch bf16 channels_last": bf16_cl,
-            "native": native}
+            "native": native, "native, native heads": native_heads}
     outs = {k: fn()[..., 0].float() for k, fn in legs.items()}
     torch.cuda.synchronize()
     dev = {k: float((v - outs["torch f32 per window"]).abs().max()) for k, v in outs.items()}
 
     times = _timed(_twice(legs), warmup, forwards)
     lines = [f"{nwin} window(s) of 100 frames; max |prediction - torch f32|: "
-             f"bf16 channels_last {dev['torch bf16 channels_last']:.2e}, native {dev['native']:.2e}"]
+             f"bf16 channels_last {dev['torch bf16 channels_last']:.2e}, native {dev['native']:.2e}, "
+             f"native heads {dev['native, native heads']:.2e}; max |native heads - native| "
+             f"{float((outs['native, native heads'] - outs['native']).abs().max()):.2e}"]
     lines += _summary(times, "torch f32 per window", nwin, "windows/s")
     nmed = float(np.mean([np.median(times[f"native ({r})"]) for r in "ab"]))
     lines.append(f"  native: {nwin * 50 / (nmed * 1e-3):.0f} source frames/s "
                  f"(50 kept of each window's 100)")
+    hmeds = [float(np.median(times[f"native, native heads ({r})"])) for r in "ab"]
+    nmeds = [float(np.median(times[f"native ({r})"])) for r in "ab"]
+    hmed = float(np.mean(hmeds))
+    spread = abs(nmeds[0] - nmeds[1])
+    lines.append(f"  native, native heads: {nwin * 50 / (hmed * 1e-3):.0f} source frames/s; "
+                 f"{nmed - hmed:+.3f} ms against native ({nmed / hmed:.2f}x), native's own "
+                 f"repeat spread {spread:.3f} ms -> "
+                 f"{'faster' if nmed - hmed > spread else 'KNOWN LOSS: not faster by more than the spread'}")
 
-    reps = 3
-    hotpath.timing_enable(True)
-    try:
-        for _ in range(reps):
-            native()
-        torch.cuda.synchronize()
-        split = {n: hotpath.timing_report(n) for n in TIMERS}
-    finally:
-        hotpath.timing_enable(False)
-    ktotal = sum(ms for ms, _ in split.values()) / reps
+    split = _kernel_split(native, TIMERS)
+    ktotal = sum(ms for ms, _ in split.values())
     flop = trunk_flop_per_frame() * 100 * nwin
-    lines.append(f"  native kernel time per forward (library timers, {reps} forwards): "
+    lines.append(f"  native kernel time per forward (library timers, 3 forwards): "
                  f"{ktotal:.3f} ms of the {nmed:.3f} ms forward; trunk {flop / 1e9:.1f} GFLOP "
                  f"-> {flop / (ktotal * 1e-3) / 1e12:.1f} TFLOP/s achieved")
     for n, (ms, count) in split.items():
-        lines.append(f"    {n}: {ms / reps:.3f} ms in {count // reps} launches, "
-                     f"{100 * ms / reps / ktotal:.1f}% of the kernel time")
+        lines.append(f"    {n}: {ms:.3f} ms in {count} launches, "
+                     f"{100 * ms / ktotal:.1f}% of the kernel time")
+    split = _kernel_split(native_heads, TIMERS + HEAD_TIMERS)
+    ktotal = sum(ms for ms, _ in split.values())
+    htotal = sum(split[n][0] for n in HEAD_TIMERS)
+    lines.append(f"  native, native heads kernel time per forward: {ktotal:.3f} ms "
+                 f"({100 * ktotal / hmed:.1f}%) of the {hmed:.3f} ms forward; head kernels "
+                 f"{htotal:.3f} ms")
+    for n, (ms, count) in split.items():
+        lines.append(f"    {n}: {ms:.3f} ms in {count} launches, "
+                     f"{100 * ms / ktotal:.1f}% of the kernel time")
     return lines
 
 
-def bench_stage(torch_model, native_model, n_frames: int, runs: int) -> list[str]:
+def bench_stage(torch_model, native_model, heads_model, n_frames: int, runs: int) -> list[str]:
     gen = np.random.default_rng(1)
     # slowly varying content with a few cuts, so windows differ
     base = gen.integers(0, 256, (8, 27, 48, 3), dtype=np.uint8)
@@ -163,9 +196,11 @@ def bench_stage(torch_model, native_model, n_frames: int, runs: int) -> list[str
     routes = {"stage route torch (f32, one window per call)":
               lambda: tstages._get_predictions(torch_model, frames, 0.4),
               "stage route native":
-              lambda: tstages._get_predictions_native(native_model, frames, 0.4)}
-    flags = {k: fn() for k, fn in routes.items()}
-    same = bool(np.array_equal(*flags.values()))
+              lambda: tstages._get_predictions_native(native_model, frames, 0.4),
+              "stage route native, native heads":
+              lambda: tstages._get_predictions_native(heads_model, frames, 0.4)}
+    flags = list({k: fn() for k, fn in routes.items()}.values())
+    same = all(np.array_equal(flags[0], f) for f in flags[1:])
     times: dict[str, list[float]] = {f"{k} ({r})": [] for r in "ab" for k in routes}
     for r in "ab":
         for _ in range(runs):
@@ -198,6 +233,8 @@ def main() -> None:
     torch_model.setup()
     native_model = TransNetV2(backend="native")
     native_model.setup()
+    heads_model = TransNetV2(backend="native", heads="native")
+    heads_model.setup()
     trunk16 = copy.deepcopy(torch_model._model.SDDCNN).to(torch.bfloat16).to(
         memory_format=torch.channels_last_3d)
 
@@ -205,9 +242,9 @@ def main() -> None:
              f"in one process, each leg twice; device {torch.cuda.get_device_name(0)}; "
              f"trunk {trunk_flop_per_frame() / 1e9:.3f} GFLOP per frame"]
     for nwin in (int(w) for w in args.windows.split(",")):
-        lines += bench_windows(torch_model, native_model, trunk16, nwin, args.warmup,
+        lines += bench_windows(torch_model, native_model, heads_model, trunk16, nwin, args.warmup,
                                args.forwards)
-    lines += bench_stage(torch_model, native_model, args.video_frames, args.stage_runs)
+    lines += bench_stage(torch_model, native_model, heads_model, args.video_frames, args.stage_runs)
     text = "\n".join(lines)
     print(text)
     if args.out:
