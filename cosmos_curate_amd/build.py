@@ -14,6 +14,8 @@ Per-file flags:
   tolerance is the f32 accumulation bound, not bit-exactness).
 - cc_tnheads.hip: -ffp-contract=off — the histogram head is bit-equal to its
   numpy restatement, and the f32 chains say fmaf where they mean it.
+- cc_attnpool.hip: default contraction (MFMA; f32 softmax within a stated
+  bound), packed-f32 instructions off.
 """
 
 from __future__ import annotations
@@ -29,6 +31,9 @@ LIB = LIBDIR / "libcchot.so"
 HIPCC = "hipcc"
 ARCH = "--offload-arch=gfx950"
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"-I{PKG.parent}"]
+# no packed-f32 instructions (v_pk_mul_f32 and kin): the f32 rescale and
+# softmax chains compile to the scalar forms
+NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 SOURCES: list[tuple[str, list[str]]] = [
     ("cc_demux.cpp", []),
@@ -41,6 +46,7 @@ SOURCES: list[tuple[str, list[str]]] = [
     ("cc_motion.hip", [ARCH]),
     ("cc_conv.hip", [ARCH]),
     ("cc_tnheads.hip", [ARCH, "-ffp-contract=off"]),
+    ("cc_attnpool.hip", [ARCH, *NO_PK_F32]),
 ]
 
 

@@ -51,6 +51,22 @@ class AttnPlan(ctypes.Structure):
 ATTN_RUNGS = ("small", "mid", "flash")  # cc_attn_plan_info.rung values
 
 
+class AttnPoolPlan(ctypes.Structure):
+    """cc_attn_pool_plan_info: how a cc_attn_pool call would be launched."""
+
+    _fields_ = [
+        ("splits", ctypes.c_int32),
+        ("chunk", ctypes.c_int32),
+        ("chunks_per_split", ctypes.c_int32),
+        ("grid", ctypes.c_int32),
+        ("block", ctypes.c_int32),
+        ("workspace_floats", ctypes.c_int64),
+    ]
+
+
+ATTN_POOL_HEADS = 16  # rows of U: cc_attn_pool's MFMA dimension
+
+
 def _declare(lib: ctypes.CDLL) -> None:
     c = ctypes
     lib.cc_last_error.restype = c.c_char_p
@@ -158,6 +174,13 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.cc_attn_mid.argtypes = lib.cc_attn.argtypes
     lib.cc_attn_flash.argtypes = lib.cc_attn.argtypes
     lib.cc_attn_rung.argtypes = [c.c_int, *lib.cc_attn.argtypes]
+    lib.cc_attn_pool_plan.argtypes = [
+        c.c_int64, c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(AttnPoolPlan)]
+    lib.cc_attn_pool_supported.argtypes = [c.c_int, c.c_int]
+    lib.cc_attn_pool.argtypes = [
+        c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64,
+        c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int, c.c_int, c.c_int,
+        c.c_void_p, c.c_int64, c.c_uint64]
     lib.cc_layernorm_bf16.argtypes = [
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
         c.c_float, c.c_uint64]
@@ -611,6 +634,87 @@ def attn_supported(heads: int, hidden: int) -> bool:
     csrc/cc_attn_plan.hpp.  Asked once per geometry."""
     plan = AttnPlan()
     return load().cc_attn_plan(1, 1, heads, hidden, ctypes.byref(plan)) == 0
+
+
+def attn_pool_plan(n: int, seq: int, heads: int, hidden: int,
+                   splits: int = 0) -> AttnPoolPlan:
+    """The launch plan of a cc_attn_pool call with these arguments
+    (cc_attn_pool_plan; host-only).  ``splits`` 0 asks for the plan's own
+    choice.  Raises on arguments cc_attn_pool itself would reject."""
+    plan = AttnPoolPlan()
+    check(load().cc_attn_pool_plan(n, seq, heads, hidden, splits,
+                                   ctypes.byref(plan)))
+    return plan
+
+
+@functools.lru_cache(maxsize=None)
+def attn_pool_supported(heads: int, hidden: int) -> bool:
+    """Whether cc_attn_pool takes this head geometry — the library's own
+    answer (csrc/cc_attnpool_plan.hpp).  Asked once per geometry."""
+    return bool(load().cc_attn_pool_supported(heads, hidden))
+
+
+def attn_pool_probe(u):
+    """f32 U [..., heads, H] (heads <= 16) as cc_attn_pool reads it: (u_hi,
+    u_lo, usum) with U zero-padded to 16 rows, u_hi + u_lo its two-term bf16
+    split and usum the f32 row sums of the f32 U."""
+    import torch
+
+    u = u.float()
+    pad = ATTN_POOL_HEADS - u.shape[-2]
+    if pad < 0:
+        raise ValueError(f"attn_pool takes at most {ATTN_POOL_HEADS} heads")
+    u = torch.nn.functional.pad(u, (0, 0, 0, pad))
+    hi = u.to(torch.bfloat16)
+    lo = (u - hi.float()).to(torch.bfloat16)
+    return hi.contiguous(), lo.contiguous(), u.sum(dim=-1).contiguous()
+
+
+def attn_pool(x, u_hi, u_lo, usum, n: int, seq: int, heads: int, *,
+              murstd=None, splits: int = 0):
+    """One-query attention pooling on the device (cc_attn_pool): the
+    softmax-weighted sums of the normalised tokens, f32 [n, heads, H].
+
+    ``x`` bf16 [n*seq, H], rows may be strided; (``u_hi``, ``u_lo``,
+    ``usum``) from attn_pool_probe, [16, H] / [16] for one probe shared by all
+    frames or [n, 16, H] / [n, 16]; ``murstd`` f32 [n*seq, 2] (mean, rstd) of
+    the rows, None for tokens that are already normalised.  No fallback: a
+    failing call raises."""
+    import torch
+
+    lib = require_gpu()
+    rows, hidden = x.shape
+    if (x.dtype != torch.bfloat16 or not x.is_cuda or rows != n * seq
+            or x.stride(1) != 1):
+        raise ValueError("x must be a (n*seq, H) bf16 device tensor with unit "
+                         "column stride")
+    shared = u_hi.dim() == 2
+    want = (ATTN_POOL_HEADS, hidden) if shared else (n, ATTN_POOL_HEADS, hidden)
+    for t in (u_hi, u_lo):
+        if (tuple(t.shape) != want or t.dtype != torch.bfloat16
+                or not t.is_contiguous()):
+            raise ValueError(f"u_hi / u_lo must be contiguous bf16 {want}")
+    if (tuple(usum.shape) != want[:-1] or usum.dtype != torch.float32
+            or not usum.is_contiguous()):
+        raise ValueError(f"usum must be contiguous f32 {want[:-1]}")
+    if murstd is not None and (
+            tuple(murstd.shape) != (rows, 2) or murstd.dtype != torch.float32
+            or not murstd.is_contiguous()):
+        raise ValueError("murstd must be contiguous f32 (n*seq, 2)")
+    plan = attn_pool_plan(n, seq, heads, hidden, splits)
+    out = torch.empty((n, heads, hidden), dtype=torch.float32, device=x.device)
+    ws = (torch.empty(plan.workspace_floats, dtype=torch.float32, device=x.device)
+          if plan.workspace_floats else None)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    check(lib.cc_attn_pool(
+        x.data_ptr(), x.stride(0) if rows > 1 else hidden,
+        murstd.data_ptr() if murstd is not None else None,
+        u_hi.data_ptr(), u_lo.data_ptr(),
+        0 if shared else ATTN_POOL_HEADS * hidden, usum.data_ptr(),
+        out.data_ptr(), n, seq, heads, hidden, splits,
+        ws.data_ptr() if ws is not None else None, plan.workspace_floats,
+        stream))
+    return out
 
 
 class VideoInfo(ctypes.Structure):

@@ -53,6 +53,20 @@ SIGLIP_MEAN = (0.5, 0.5, 0.5)  # SiglipImageProcessor defaults
 SIGLIP_STD = (0.5, 0.5, 0.5)
 
 RESIZE_MODES = ("cubic", "antialias")
+POOL_HEADS = ("torch", "native")
+
+
+def check_pool_head(pool_head: str, variant: str) -> str:
+    """``pool_head`` of an image tower: "torch" (default) or "native", the
+    one-query pooling kernel (cc_attn_pool) — which only a tower with a
+    pooling head can take, so a CLIP variant refuses it."""
+    if pool_head not in POOL_HEADS:
+        raise ValueError(f"pool_head must be one of {POOL_HEADS}, got {pool_head!r}")
+    if pool_head == "native" and not variant.startswith("siglip"):
+        raise ValueError(
+            f"pool_head 'native' needs a tower with an attention-pooling head "
+            f"(a siglip_* variant); {variant!r} pools its class token")
+    return pool_head
 
 
 def check_resize_mode(resize: str) -> str:
@@ -66,13 +80,14 @@ class _CLIPImageEmbeddings(torch.nn.Module):
 
     def __init__(self, variant: str = "vit_b32",
                  checkpoint_path: str | None = None,
-                 resize: str = "cubic") -> None:
+                 resize: str = "cubic", pool_head: str = "torch") -> None:
         super().__init__()
         import os
 
         from cosmos_curate_amd.models import clip_weights as cw
 
         self._resize = check_resize_mode(resize)
+        check_pool_head(pool_head, variant)
 
         hotpath.require_gpu()  # fail loudly before any lazy surprises
         self.device = torch.device("cuda")
@@ -89,6 +104,13 @@ class _CLIPImageEmbeddings(torch.nn.Module):
                 pretrained or cw.make_siglip_weights(cfg), cfg).to(self.device)
             self._mean_arr = np.array(SIGLIP_MEAN, dtype=np.float32)
             self._std_arr = np.array(SIGLIP_STD, dtype=np.float32)
+            if pool_head == "native":
+                if not hotpath.attn_pool_supported(cfg.heads, cfg.hidden):
+                    # asked for by name: refused, not downgraded
+                    raise ValueError(
+                        f"pool_head 'native': cc_attn_pool does not take "
+                        f"{cfg.heads} heads at width {cfg.hidden}")
+                self.tower.native_pool = True
         else:
             sd = pretrained or (
                 make_clip_vit_b32_weights() if variant == "vit_b32"
@@ -202,13 +224,18 @@ class CLIPImageEmbeddings(ModelInterface):
     resize: how frames of another size than the tower's are brought to it,
     "cubic" (default) or "antialias" (the reference's chain; module
     docstring).
+    pool_head: "torch" (default) or "native": a SigLIP tower's MAP head on
+    the one-query pooling kernel (cc_attn_pool); refused for a CLIP variant
+    here and, without the GPU library or for a width it does not take, at
+    setup().
     """
 
     def __init__(self, variant: str = "vit_b32",
                  checkpoint_path: str | None = None,
-                 resize: str = "cubic") -> None:
+                 resize: str = "cubic", pool_head: str = "torch") -> None:
         super().__init__()
         self._resize = check_resize_mode(resize)
+        self._pool_head = check_pool_head(pool_head, variant)
         self._variant = variant
         self._checkpoint_path = checkpoint_path
         self._model: _CLIPImageEmbeddings | None = None
@@ -224,7 +251,8 @@ class CLIPImageEmbeddings(ModelInterface):
     def setup(self) -> None:
         self._model = _CLIPImageEmbeddings(self._variant,
                                            checkpoint_path=self._checkpoint_path,
-                                           resize=self._resize)
+                                           resize=self._resize,
+                                           pool_head=self._pool_head)
 
     def __call__(self, images: torch.Tensor | npt.NDArray[np.uint8]) -> torch.Tensor:
         assert self._model is not None, "setup() not called"

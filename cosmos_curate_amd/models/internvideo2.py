@@ -34,7 +34,10 @@ _INTERNVIDEO2_MODEL_ID = "OpenGVLab/InternVideo2-Stage2_1B-224p-f4"
 class InternVideo2MultiModality(ModelInterface):
     """``utils_only``: frame preparation only, no tower (the frame-creation
     stage's instance).  ``tower``: a ready tower to use instead of building
-    one (tests inject a 2-block tower)."""
+    one (tests inject a 2-block tower).  ``pool_head``: "native" puts the
+    tower's pooling head on cc_attn_pool at setup(), refused there without
+    the GPU library or for a width it does not take; "torch" (default)
+    leaves the tower as it is."""
 
     def __init__(
         self,
@@ -43,8 +46,12 @@ class InternVideo2MultiModality(ModelInterface):
         num_frames: int = iw.INTERNVIDEO2_1B.num_frames,
         checkpoint_path: str | None = None,
         tower: torch.nn.Module | None = None,
+        pool_head: str = "torch",
     ) -> None:
         super().__init__()
+        if pool_head not in ("torch", "native"):
+            raise ValueError(f"pool_head must be 'torch' or 'native', got {pool_head!r}")
+        self._pool_head = pool_head
         self.utils_only = utils_only
         self._cfg = (tower.cfg if tower is not None else
                      dataclasses.replace(iw.INTERNVIDEO2_1B, num_frames=num_frames))
@@ -60,15 +67,24 @@ class InternVideo2MultiModality(ModelInterface):
         return [_INTERNVIDEO2_MODEL_ID]
 
     def setup(self) -> None:
-        if self.utils_only or self._tower is not None:
+        if self.utils_only:
             return
-        from cosmos_curate_amd.models.internvideo2_vit import InternVideo2VisionTowerAMD
+        if self._tower is None:
+            from cosmos_curate_amd.models.internvideo2_vit import InternVideo2VisionTowerAMD
 
-        hotpath.require_gpu()  # fail loudly before any lazy surprises
-        path = self._checkpoint_path or os.environ.get("CC_IV2_CHECKPOINT")
-        sd = (iw.load_internvideo2_state_dict(path) if path
-              else iw.make_internvideo2_weights(self._cfg))
-        self._tower = InternVideo2VisionTowerAMD(sd, self._cfg).to("cuda")
+            hotpath.require_gpu()  # fail loudly before any lazy surprises
+            path = self._checkpoint_path or os.environ.get("CC_IV2_CHECKPOINT")
+            sd = (iw.load_internvideo2_state_dict(path) if path
+                  else iw.make_internvideo2_weights(self._cfg))
+            self._tower = InternVideo2VisionTowerAMD(sd, self._cfg).to("cuda")
+        if self._pool_head == "native":
+            hotpath.require_gpu()
+            if not hotpath.attn_pool_supported(self._cfg.pool_heads, self._cfg.hidden):
+                # asked for by name: refused, not downgraded
+                raise ValueError(
+                    f"pool_head 'native': cc_attn_pool does not take "
+                    f"{self._cfg.pool_heads} heads at width {self._cfg.hidden}")
+            self._tower.native_pool = True
 
     def get_target_num_frames(self) -> int:
         return self._cfg.num_frames

@@ -56,12 +56,16 @@ from __future__ import annotations
 
 import torch
 
+from cosmos_curate_amd import hotpath
 from cosmos_curate_amd.models import internvideo2_weights as iw
 from cosmos_curate_amd.models.vit_encoder import (
     VitEncoderAMD,
     cc_linear_ln,
+    cc_ln_murstd,
+    cc_ln_stats,
     fold_layernorm,
     patchify,
+    pool_head_native,
 )
 
 
@@ -75,9 +79,39 @@ def fold_layerscale(
             (g * b.float()).contiguous())
 
 
+def fold_pool_head(
+    wk: torch.Tensor, gamma_k: torch.Tensor, wv: torch.Tensor,
+    bv: torch.Tensor, gamma_v: torch.Tensor, beta_v: torch.Tensor, heads: int,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The pooling head's weights as its one-query form reads them (DESIGN.md
+    §23), in float64: (W_k * gamma_k per input column as [heads, hd, H], the
+    same of W_v with gamma_v, W_v beta_v + b_v).  LayerNorm_k's beta and the
+    K bias move every score of a head by one constant, which the softmax
+    cancels; the softmax weights sum to 1, so LayerNorm_v's beta and the V
+    bias come out of the pooling unchanged."""
+    H = wk.shape[1]
+    hd = H // heads
+    uk = (wk.double() * gamma_k.double()[None, :]).reshape(heads, hd, H)
+    wvf = (wv.double() * gamma_v.double()[None, :]).reshape(heads, hd, H)
+    return uk, wvf, wv.double() @ beta_v.double() + bv.double()
+
+
+def pool_probe(q: torch.Tensor, uk: torch.Tensor) -> torch.Tensor:
+    """U [n, heads, H] = gamma_k * (W_k,h^T q_h) of the clips' scaled queries
+    q (n, heads, hd): score[t, h] = U_h . xhat_t plus a per-head constant."""
+    return torch.einsum("nhd,hdk->nhk", q, uk)
+
+
 class InternVideo2VisionTowerAMD(VitEncoderAMD):
     """(B, T, 3, image, image) pixels or prebuilt patch rows -> (B, proj)
-    f32 unit-norm video embeddings."""
+    f32 unit-norm video embeddings.
+
+    ``native_pool`` (default False): True runs the pooling head's attention
+    on cc_attn_pool where the library takes the width — the [tokens, 2H] K/V
+    GEMM is not launched; False, CPU tensors and other widths take the K/V
+    GEMM and the torch f32 softmax."""
+
+    native_pool = False
 
     def __init__(
         self,
@@ -132,6 +166,15 @@ class InternVideo2VisionTowerAMD(VitEncoderAMD):
         reg("pool_bo", to_f32(sd[cp + "cross_attn.proj.bias"]))
         reg("vproj_w", to_f32(sd["vision_proj.weight"]))
         reg("vproj_b", to_f32(sd["vision_proj.bias"]))
+        # cc_attn_pool's route: LayerNorm_k's gamma on W_k, LayerNorm_v on W_v
+        uk, wvf, bvf = fold_pool_head(
+            *(sd[cp + k] for k in (
+                "cross_attn.k.weight", "norm1_k.weight", "cross_attn.v.weight",
+                "cross_attn.v_bias", "norm1_v.weight", "norm1_v.bias")),
+            cfg.pool_heads)
+        reg("pool_uk", uk.float().contiguous(), persistent=False)
+        reg("pool_wvf", wvf.float().contiguous(), persistent=False)
+        reg("pool_bvf", bvf.float().contiguous(), persistent=False)
 
     def _patch_weight(self, sd: dict[str, torch.Tensor]) -> torch.Tensor:
         # [H, 3, 1, P, P]: tubelet 1, so the 3-D conv is a per-frame GEMM
@@ -160,12 +203,44 @@ class InternVideo2VisionTowerAMD(VitEncoderAMD):
             "kn_w": sd[b + "attn.k_norm.weight"],
         }
 
+    def _pool_query(self, h: torch.Tensor, n: int, seq: int) -> torch.Tensor:
+        """The clip's scaled query (n, heads, hd) f32: LayerNorm_q of the
+        token mean through the q projection."""
+        cfg = self.cfg
+        H = cfg.hidden
+        hd = H // cfg.pool_heads
+        q = torch.nn.functional.layer_norm(
+            h.reshape(n, seq, H).float().mean(dim=1), (H,), self.pool_lnq_w,
+            self.pool_lnq_b, eps=cfg.pool_ln_eps)
+        q = (q @ self.pool_wq.T + self.pool_bq) * hd ** -0.5
+        return q.reshape(n, cfg.pool_heads, hd)
+
+    def _pool_native(self, h: torch.Tensor, stats: torch.Tensor | None, n: int,
+                     seq: int) -> torch.Tensor:
+        """clip_projector's attention on cc_attn_pool: no K/V
+        GEMM; the raw tokens with their LayerNorm statistics, one small
+        matmul per call for U, and the V projection on the pooled rows."""
+        cfg = self.cfg
+        u_hi, u_lo, usum = hotpath.attn_pool_probe(
+            pool_probe(self._pool_query(h, n, seq), self.pool_uk))
+        if stats is None:
+            stats = cc_ln_stats(h)
+        zhat = hotpath.attn_pool(
+            h, u_hi, u_lo, usum, n, seq, cfg.pool_heads,
+            murstd=cc_ln_murstd(stats, cfg.pool_ln_eps))
+        o = torch.einsum("nhk,hdk->nhd", zhat, self.pool_wvf)
+        return o.reshape(n, cfg.hidden) + self.pool_bvf
+
     def _pool(self, h: torch.Tensor, stats: torch.Tensor | None, n: int,
               seq: int) -> torch.Tensor:
         """clip_projector + vision_proj: (n*seq, H) -> (n, proj) f32."""
         cfg = self.cfg
         H = cfg.hidden
         hd = H // cfg.pool_heads
+        if pool_head_native(self, h, cfg.pool_heads):
+            o = self._pool_native(h, stats, n, seq)
+            o = o @ self.pool_wo.T + self.pool_bo
+            return o @ self.vproj_w.T + self.vproj_b
         if stats is not None:
             kv = cc_linear_ln(h, stats, self.wf_pool_kv, self.s_pool_kv,
                               self.c_pool_kv, 0, cfg.pool_ln_eps)
@@ -178,11 +253,7 @@ class InternVideo2VisionTowerAMD(VitEncoderAMD):
         kv = kv.reshape(n, seq, 2, cfg.pool_heads, hd).float()
         k = kv[:, :, 0].transpose(1, 2)  # (n, heads, seq, hd)
         v = kv[:, :, 1].transpose(1, 2)
-        q = torch.nn.functional.layer_norm(
-            h.reshape(n, seq, H).float().mean(dim=1), (H,), self.pool_lnq_w,
-            self.pool_lnq_b, eps=cfg.pool_ln_eps)
-        q = (q @ self.pool_wq.T + self.pool_bq) * hd ** -0.5
-        q = q.reshape(n, cfg.pool_heads, 1, hd)
+        q = self._pool_query(h, n, seq).unsqueeze(2)  # (n, heads, 1, hd)
         att = torch.softmax(q @ k.transpose(-1, -2), dim=-1)
         o = (att @ v).reshape(n, H)
         o = o @ self.pool_wo.T + self.pool_bo

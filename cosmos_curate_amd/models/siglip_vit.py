@@ -19,19 +19,45 @@ the shared encoder (vit_encoder.VitEncoderAMD) — the same HIP kernels as
 the CLIP tower, with the activation and LN eps read from the VitConfig.
 This file keeps what is SigLIP's own: the patch bias and position add,
 post-LN, and the tiny MAP head (1 query per frame), which runs in torch
-f32.
+f32 — or, under ``native_pool``, its attention over the tokens on
+cc_attn_pool and only its O(frames) layers in torch.
 """
 
 from __future__ import annotations
 
 import torch
 
+from cosmos_curate_amd import hotpath
 from cosmos_curate_amd.models import clip_weights as cw
-from cosmos_curate_amd.models.vit_encoder import VitEncoderAMD
+from cosmos_curate_amd.models.vit_encoder import VitEncoderAMD, pool_head_native
+
+
+def fold_map_probe(
+    probe: torch.Tensor, in_proj_w: torch.Tensor, in_proj_b: torch.Tensor,
+    heads: int,
+) -> torch.Tensor:
+    """The MAP head's K projection collapsed onto its one query (DESIGN.md
+    §23): U [heads, H] f64 with U_h = W_k,h^T q_h * hd^-1/2 and q = W_q probe
+    + b_q, so that the score of token x for head h is U_h . x plus a constant
+    (q_h . b_k,h) that the softmax cancels.  Pure arithmetic on the
+    checkpoint, in float64."""
+    H = probe.shape[-1]
+    hd = H // heads
+    wq, wk, _ = in_proj_w.double().chunk(3, dim=0)
+    bq = in_proj_b.double()[:H]
+    q = (wq @ probe.double().reshape(H) + bq).reshape(heads, hd) * hd ** -0.5
+    return torch.einsum("hd,hdk->hk", q, wk.reshape(heads, hd, H))
 
 
 class SiglipVisionTowerAMD(VitEncoderAMD):
-    """SigLIP vision tower + MAP pooling head, bf16 MFMA path."""
+    """SigLIP vision tower + MAP pooling head, bf16 MFMA path.
+
+    ``native_pool`` (default False): True runs the probe's attention over the
+    tokens on cc_attn_pool, straight off the bf16 post-LN tokens, where the
+    library takes the width; the O(frames) rest of the head stays in torch
+    f32.  False, CPU tensors and other widths take the torch f32 head."""
+
+    native_pool = False
 
     def __init__(self, sd: dict[str, torch.Tensor],
                  cfg: cw.VitConfig = cw.SIGLIP_L16_256) -> None:
@@ -53,22 +79,44 @@ class SiglipVisionTowerAMD(VitEncoderAMD):
         reg("h_fc1_b", sd["head.mlp.fc1.bias"].float().contiguous())
         reg("h_fc2_w", sd["head.mlp.fc2.weight"].float().contiguous())
         reg("h_fc2_b", sd["head.mlp.fc2.bias"].float().contiguous())
+        # the probe's K projection collapsed for cc_attn_pool (derived, so
+        # kept out of the state dict)
+        u = fold_map_probe(self.probe, self.h_inproj_w, self.h_inproj_b, self.heads)
+        for name, t in zip(("hi", "lo", "sum"), hotpath.attn_pool_probe(u)):
+            reg(f"h_u_{name}", t, persistent=False)
+
+    def _map_attend_native(self, x: torch.Tensor) -> torch.Tensor:
+        """The probe's attention output (B, 1, H) f32 on cc_attn_pool: the
+        pooled tokens per head, then that head's V projection."""
+        cfg = self.cfg
+        B, seq, H = x.shape
+        hd = H // self.heads
+        zhat = hotpath.attn_pool(
+            x.reshape(B * seq, H), self.h_u_hi, self.h_u_lo, self.h_u_sum, B,
+            seq, self.heads)
+        wv = self.h_inproj_w[2 * H:].reshape(self.heads, hd, H)
+        o = torch.einsum("bhk,hdk->bhd", zhat, wv).reshape(B, 1, cfg.hidden)
+        return o + self.h_inproj_b[2 * H:]
 
     def _map_head(self, x: torch.Tensor) -> torch.Tensor:
-        """MAP pooling head (SiglipMultiheadAttentionPoolingHead), torch
-        f32: probe cross-attention over the (B, seq, H) tokens."""
+        """MAP pooling head (SiglipMultiheadAttentionPoolingHead): probe
+        cross-attention over the (B, seq, H) tokens — cc_attn_pool under
+        ``native_pool``, else torch f32 — and its dense tail in torch f32."""
         cfg = self.cfg
         B = x.shape[0]
         hd = cfg.hidden // self.heads
-        xf = x.float()
-        probe = self.probe.expand(B, 1, cfg.hidden)
-        wq, wk, wv = self.h_inproj_w.chunk(3, dim=0)
-        bq, bk, bv = self.h_inproj_b.chunk(3, dim=0)
-        q = (probe @ wq.T + bq).reshape(B, 1, self.heads, hd).transpose(1, 2)
-        k = (xf @ wk.T + bk).reshape(B, -1, self.heads, hd).transpose(1, 2)
-        v = (xf @ wv.T + bv).reshape(B, -1, self.heads, hd).transpose(1, 2)
-        att = torch.softmax((q @ k.transpose(-1, -2)) * (hd ** -0.5), dim=-1)
-        o = (att @ v).transpose(1, 2).reshape(B, 1, cfg.hidden)
+        if pool_head_native(self, x, self.heads):
+            o = self._map_attend_native(x)
+        else:
+            xf = x.float()
+            probe = self.probe.expand(B, 1, cfg.hidden)
+            wq, wk, wv = self.h_inproj_w.chunk(3, dim=0)
+            bq, bk, bv = self.h_inproj_b.chunk(3, dim=0)
+            q = (probe @ wq.T + bq).reshape(B, 1, self.heads, hd).transpose(1, 2)
+            k = (xf @ wk.T + bk).reshape(B, -1, self.heads, hd).transpose(1, 2)
+            v = (xf @ wv.T + bv).reshape(B, -1, self.heads, hd).transpose(1, 2)
+            att = torch.softmax((q @ k.transpose(-1, -2)) * (hd ** -0.5), dim=-1)
+            o = (att @ v).transpose(1, 2).reshape(B, 1, cfg.hidden)
         o = o @ self.h_outproj_w.T + self.h_outproj_b
         res = o
         o = torch.nn.functional.layer_norm(

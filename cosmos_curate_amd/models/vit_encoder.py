@@ -149,6 +149,28 @@ def cc_ln_stats(x: torch.Tensor) -> torch.Tensor:
     return stats
 
 
+def cc_ln_murstd(stats: torch.Tensor, eps: float) -> torch.Tensor:
+    """(mean, rstd) per row, f32 [M, 2], of a LayerNorm at ``eps`` from the
+    row statistics [M, H/64, 2] (cc_ln_finalize) — what cc_attn_pool reads."""
+    lib = hotpath.require_gpu()
+    assert stats.dtype == torch.float32 and stats.is_contiguous()
+    M, blocks, _ = stats.shape
+    murstd = torch.empty((M, 2), dtype=torch.float32, device=stats.device)
+    stream = torch.cuda.current_stream(stats.device).cuda_stream
+    hotpath.check(
+        lib.cc_ln_finalize(stats.data_ptr(), M, blocks * 64, 1, eps,
+                           murstd.data_ptr(), stream))
+    return murstd
+
+
+def pool_head_native(tower: torch.nn.Module, t: torch.Tensor, heads: int) -> bool:
+    """Whether a tower's one-query pooling head runs cc_attn_pool on ``t``:
+    the tower's ``native_pool`` is set, ``t`` is on the GPU and the library
+    takes the geometry.  Otherwise the head stays on its torch f32 code."""
+    return (tower.native_pool and t.is_cuda
+            and hotpath.attn_pool_supported(heads, tower.cfg.hidden))
+
+
 def cc_linear_ln(
     x: torch.Tensor,
     stats: torch.Tensor,

@@ -131,13 +131,16 @@ class ClipEmbeddingStage(CuratorStage):
         variant: str = "vit_b32",
         checkpoint_path: str | None = None,
         resize: str = "cubic",
+        pool_head: str = "torch",
     ) -> None:
         """``variant``: the tower, a key of clip_weights.CONFIGS (the
         embedding width follows it: 512 / 768 / 1024 / 1152);
         ``checkpoint_path``: a local checkpoint for it, else the
         deterministic stand-in weights; ``resize``: how frames of another
         size than the tower's are brought to it, "cubic" or "antialias"
-        (models/clip.py)."""
+        (models/clip.py); ``pool_head``: "native" runs a SigLIP tower's
+        pooling head on the one-query attention kernel (a CLIP variant
+        refuses it), "torch" keeps the f32 head."""
         self._resize = resize
         self._timer = StageTimer(self)
         self._num_gpus = num_gpus_per_worker
@@ -145,7 +148,7 @@ class ClipEmbeddingStage(CuratorStage):
         self._verbose = verbose
         self._log_stats = log_stats
         self._model = CLIPImageEmbeddings(variant, checkpoint_path=checkpoint_path,
-                                          resize=resize)
+                                          resize=resize, pool_head=pool_head)
 
     @property
     def resources(self) -> CuratorStageResource:

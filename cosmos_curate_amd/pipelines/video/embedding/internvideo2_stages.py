@@ -128,6 +128,17 @@ class InternVideo2EmbeddingStage(CuratorStage):
         self._log_stats = log_stats
         self._model = InternVideo2MultiModality()
 
+    @classmethod
+    def with_pool_head(cls, pool_head: str, **kwargs) -> "InternVideo2EmbeddingStage":
+        """The stage with ``pool_head`` "native": the tower's pooling head on
+        the one-query attention kernel (cc_attn_pool) instead of the K/V GEMM
+        and the f32 softmax; "torch" is the plain stage.  The constructor
+        keeps the reference's signature, so the knob comes in here; ``kwargs``
+        are the constructor's."""
+        stage = cls(**kwargs)
+        stage._model = InternVideo2MultiModality(pool_head=pool_head)
+        return stage
+
     @property
     def model(self) -> ModelInterface:
         return self._model

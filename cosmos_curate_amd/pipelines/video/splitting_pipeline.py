@@ -230,7 +230,10 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
 
         stages.append(InternVideo2FrameCreationStage(
             target_fps=args.target_clip_fps, log_stats=True))
-        stages.append(InternVideo2EmbeddingStage(log_stats=True))
+        pool = _pool_kw(args)
+        stages.append(
+            InternVideo2EmbeddingStage.with_pool_head(pool["pool_head"], log_stats=True)
+            if pool else InternVideo2EmbeddingStage(log_stats=True))
     elif args.generate_embeddings:
         res = args.clip_extraction_target_res
         stages.append(ClipFrameCreationStage(
@@ -239,11 +242,18 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
             log_stats=True,
         ))
         stages.append(ClipEmbeddingStage(
-            log_stats=True, variant=args.embedding_model, **_resize_kw(args)))
+            log_stats=True, variant=args.embedding_model, **_resize_kw(args),
+            **_pool_kw(args)))
     stages.append(ClipWriterStage(
         args.output_clip_path, log_stats=True,
         **({"embedding_algorithm": "internvideo2"} if iv2 else {})))
     return stages
+
+
+def _pool_kw(args: argparse.Namespace) -> dict:
+    """--embedding-pool-head as the stages' keyword; nothing at the default."""
+    pool = getattr(args, "embedding_pool_head", "torch")
+    return {} if pool == "torch" else {"pool_head": pool}
 
 
 def _resize_kw(args: argparse.Namespace) -> dict:
@@ -305,6 +315,12 @@ def _setup_parser(parser: argparse.ArgumentParser) -> None:
                         "CenterCrop, what source-resolution frames "
                         "(--clip-extraction-target-res -1) want; ignored "
                         "under --embedding-algorithm internvideo2")
+    parser.add_argument("--embedding-pool-head", default="torch",
+                        choices=["torch", "native"],
+                        help="torch: the embedding tower's attention-pooling "
+                        "head in f32 torch; native: on the one-query pooling "
+                        "kernel (SigLIP towers and internvideo2; a CLIP "
+                        "--embedding-model has no such head and refuses it)")
     parser.add_argument("--aesthetic-threshold", type=float, default=None)
     parser.add_argument("--clip-extraction-target-res", type=int, default=224,
                         help="square target resolution for extracted frames; "

@@ -455,6 +455,44 @@ int cc_attn_cls(const void* q, const void* k, const void* v, int64_t ldkv,
                 void* out, int64_t n_frames, int seq, int heads, int hidden,
                 float scale, uint64_t stream);
 
+/* ---- one-query attention pooling (SigLIP's MAP probe, InternVideo2's
+ * clip_projector).  With one query per (frame, head) the K
+ * projection collapses into U [16, H] (row h = gamma_k * (W_k,h^T q_h), rows
+ * from `heads` on zero) and the V projection moves behind the pooling, so the
+ * kernel reads the raw tokens once:
+ *   score[t,h] = rstd_t * (U_h . x_t - mu_t * usum_h)
+ *   zhat[f,h,:] = sum_t softmax_t(score)[t,h] * rstd_t * (x_t - mu_t)
+ * x bf16, token t of frame f at x + (f*seq + t)*ldx (ldx >= H, ldx % 8 == 0);
+ * murstd f32 [n*seq, 2] = (mean, rstd) as cc_ln_finalize writes it, or null
+ * for (0, 1); u_hi + u_lo = the two-term bf16 split of the f32 U, frame f's
+ * at u + f*u_stride elements (u_stride 0: one probe for all frames, else
+ * >= 16*H); usum f32 = the row sums of the f32 U, 16 per frame (per call at
+ * u_stride 0); zhat f32 [n, heads, H].  splits 0 = the plan's choice; with
+ * more than one split the partials go through `workspace` (f32, at least
+ * cc_attn_pool_plan's workspace_floats elements, else may be null) and a
+ * second kernel adds them in split order.  No atomics: bit-identical from
+ * run to run.  Timed as "attn_pool" (and "attn_pool_combine").
+ * heads <= 16, H a multiple of 128 up to 1408, else CC_ERR_UNSUPPORTED;
+ * CC_ERR_INVALID on null or misaligned (16 bytes) pointers, non-positive
+ * n/seq, a bad ldx/u_stride or a workspace too small — all before any
+ * launch. */
+typedef struct cc_attn_pool_plan_info {
+  int32_t splits;            /* workgroups per frame */
+  int32_t chunk;             /* tokens per staged chunk */
+  int32_t chunks_per_split;  /* a split's tokens = chunk * this */
+  int32_t grid;              /* workgroups launched (n * splits) */
+  int32_t block;             /* threads per workgroup */
+  int64_t workspace_floats;  /* f32 elements of workspace (0 at splits 1) */
+} cc_attn_pool_plan_info;
+int cc_attn_pool_plan(int64_t n, int seq, int heads, int H, int splits,
+                      cc_attn_pool_plan_info* out);
+int cc_attn_pool_supported(int heads, int H); /* 1 or 0; host-only */
+int cc_attn_pool(const void* x, int64_t ldx, const float* murstd,
+                 const void* u_hi, const void* u_lo, int64_t u_stride,
+                 const float* usum, float* zhat, int64_t n, int seq, int heads,
+                 int H, int splits, float* workspace, int64_t workspace_floats,
+                 uint64_t stream);
+
 /* ---- fused bf16 LayerNorm (replaces torch layer_norm in the ViT
  * forward; f32 stats/affine; H = 128, 1152, 1408 or one of the
  * instantiated multiples of 256: 256, 512, 768, 1024, 2048, 3072, 4096). */
