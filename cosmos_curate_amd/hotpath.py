@@ -67,6 +67,24 @@ class AttnPoolPlan(ctypes.Structure):
 ATTN_POOL_HEADS = 16  # rows of U: cc_attn_pool's MFMA dimension
 
 
+class KmeansPlan(ctypes.Structure):
+    """cc_kmeans_plan_info: how a k-means step would be launched."""
+
+    _fields_ = [
+        ("tile_rows", ctypes.c_int32),
+        ("tile_cents", ctypes.c_int32),
+        ("cent_tiles", ctypes.c_int32),
+        ("d_chunks", ctypes.c_int32),
+        ("assign_grid", ctypes.c_int32),
+        ("assign_block", ctypes.c_int32),
+        ("piece_rows", ctypes.c_int32),
+        ("pieces", ctypes.c_int32),
+        ("acc_block", ctypes.c_int32),
+        ("combine_grid_y", ctypes.c_int32),
+        ("workspace_bytes", ctypes.c_int64),
+    ]
+
+
 def _declare(lib: ctypes.CDLL) -> None:
     c = ctypes
     lib.cc_last_error.restype = c.c_char_p
@@ -209,6 +227,16 @@ def _declare(lib: ctypes.CDLL) -> None:
         c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_float, c.c_uint64]
     lib.cc_pairwise_max_earlier.argtypes = [
         c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_uint64]
+    lib.cc_kmeans_plan.argtypes = [
+        c.c_int64, c.c_int64, c.c_int64, c.POINTER(KmeansPlan)]
+    lib.cc_kmeans_workspace_bytes.argtypes = [c.c_int64, c.c_int64, c.c_int64]
+    lib.cc_kmeans_workspace_bytes.restype = c.c_int64
+    lib.cc_kmeans_assign.argtypes = [
+        c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p,
+        c.c_void_p, c.c_uint64]
+    lib.cc_kmeans_accumulate.argtypes = [
+        c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64,
+        c.c_void_p, c.c_void_p, c.c_int64, c.c_uint64]
     lib.cc_conv3x3_bf16.argtypes = [
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int,
         c.c_int, c.c_int, c.c_uint64]
@@ -715,6 +743,15 @@ def attn_pool(x, u_hi, u_lo, usum, n: int, seq: int, heads: int, *,
         ws.data_ptr() if ws is not None else None, plan.workspace_floats,
         stream))
     return out
+
+
+def kmeans_plan(m: int, d: int, k: int) -> KmeansPlan:
+    """The launch plan of a k-means step on e [m, d] and k centroids
+    (cc_kmeans_plan; host-only).  Raises on shapes cc_kmeans_assign itself
+    would reject."""
+    plan = KmeansPlan()
+    check(load().cc_kmeans_plan(m, d, k, ctypes.byref(plan)))
+    return plan
 
 
 class VideoInfo(ctypes.Structure):

@@ -17,8 +17,11 @@ rebuilt MI355X-native (BASELINE config #5):
   (farther-from-centroid) row exceeds 1 - eps.
 
 No CPU fallback: ``pairwise_max_earlier`` requires the HIP extension +
-GPU.  ``kmeans`` is plain torch and runs wherever its tensors live —
-the world_size-2 gloo test drives the collective path on CPU.
+GPU.  ``kmeans`` is plain torch by default and runs wherever its tensors
+live — the world_size-2 gloo test drives the collective path on CPU; with
+``backend="native"`` its assign and accumulate steps run on
+csrc/cc_kmeans.hip (exact-f32 MFMA argmax, atomic-free f64 sums) and need
+the GPU like the scan.
 """
 
 from __future__ import annotations
@@ -39,6 +42,74 @@ class SemDedupConfig:
     n_iters: int = 20
     eps: float = 0.01
     random_seed: int = 0x5EED
+    kmeans_backend: str = "torch"  # or "native": csrc/cc_kmeans.hip
+
+
+KMEANS_BACKENDS = ("torch", "native")
+
+
+def _kmeans_operand(t: torch.Tensor, name: str) -> torch.Tensor:
+    if t.dtype != torch.float32 or t.dim() != 2:
+        raise ValueError(f"{name} must be a 2-d float32 tensor")
+    if not t.is_cuda:  # the kernels take device pointers only
+        raise hotpath.HotpathUnavailableError(
+            f"{name} must be a device tensor: the native k-means step has no CPU path")
+    return t.contiguous()
+
+
+def kmeans_assign(e: torch.Tensor, cent: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """labels[i] = argmax_c e_i . cent_c on the exact-f32 MFMA
+    (cc_kmeans_assign), the smallest c among equal dot products; the [m, k]
+    similarities are never stored.
+
+    e (m, d) and cent (k, d) f32 device tensors, d a multiple of 64 in
+    [64, 1152].  Returns (labels int64 [m], best f32 [m] = the winning dot
+    product).  No fallback: a shape the kernel refuses raises."""
+    lib = hotpath.require_gpu()
+    e, cent = _kmeans_operand(e, "e"), _kmeans_operand(cent, "cent")
+    (m, d), k = e.shape, cent.shape[0]
+    if cent.shape[1] != d:
+        raise ValueError(f"cent has {cent.shape[1]} columns, e has {d}")
+    labels = torch.empty(m, dtype=torch.int32, device=e.device)
+    best = torch.empty(m, dtype=torch.float32, device=e.device)
+    stream = torch.cuda.current_stream(e.device).cuda_stream
+    hotpath.check(lib.cc_kmeans_assign(
+        e.data_ptr(), m, d, cent.data_ptr(), k, labels.data_ptr(),
+        best.data_ptr(), stream))
+    return labels.long(), best
+
+
+def kmeans_accumulate(
+    e: torch.Tensor, labels: torch.Tensor, k: int
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """Per-cluster f64 row sums and counts (cc_kmeans_accumulate): the
+    index_add_ of the torch loop without floating-point atomics, so two calls
+    on the same input agree bit for bit.
+
+    e (m, d) f32 device tensor, labels integer [m] with values in [0, k).
+    The stable sort of the labels and the clusters' offsets into it are
+    torch integer plumbing (sort, searchsorted) that never synchronises with
+    the host.  Returns (sums f64 [k, d], counts f64 [k]).  No fallback."""
+    lib = hotpath.require_gpu()
+    e = _kmeans_operand(e, "e")
+    m, d = e.shape
+    if labels.shape != (m,) or labels.device != e.device:
+        raise ValueError("labels must be [m] on e's device")
+    ws_bytes = lib.cc_kmeans_workspace_bytes(m, d, k)
+    if ws_bytes < 0:
+        hotpath.check(ws_bytes)
+    sorted_labels, order = torch.sort(labels, stable=True)
+    offsets = torch.searchsorted(
+        sorted_labels, torch.arange(k + 1, dtype=labels.dtype, device=e.device)
+    ).to(torch.int32)
+    order = order.to(torch.int32)
+    sums = torch.empty((k, d), dtype=torch.float64, device=e.device)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=e.device)
+    stream = torch.cuda.current_stream(e.device).cuda_stream
+    hotpath.check(lib.cc_kmeans_accumulate(
+        e.data_ptr(), m, d, order.data_ptr(), offsets.data_ptr(), k,
+        sums.data_ptr(), ws.data_ptr(), ws_bytes, stream))
+    return sums, (offsets[1:] - offsets[:-1]).to(torch.float64)
 
 
 def kmeans_fit(
@@ -47,6 +118,7 @@ def kmeans_fit(
     n_iters: int = 20,
     seed: int = 0x5EED,
     process_group=None,
+    backend: str = "torch",
 ) -> tuple[torch.Tensor, torch.Tensor]:
     """Spherical k-means over (possibly rank-sharded) embeddings.
 
@@ -57,8 +129,15 @@ def kmeans_fit(
     compute the same init when fed identical full data (single rank) or
     receive rank-0's init via broadcast (multi rank).
 
+    ``backend="native"`` runs assignment and the per-cluster sums on the HIP
+    kernels (kmeans_assign, kmeans_accumulate) and needs device tensors and
+    a ``d`` they take; it raises otherwise, it never falls back.  Init,
+    broadcast, all-reduce and the normalise tail are shared.
+
     Returns (centroids [k,d] unit rows, local labels [m]).
     """
+    if backend not in KMEANS_BACKENDS:
+        raise ValueError(f"backend must be one of {KMEANS_BACKENDS}, got {backend!r}")
     e = torch.nn.functional.normalize(emb.float(), dim=1, eps=1e-12)
     m, d = e.shape
     dist = torch.distributed if process_group is not None else None
@@ -74,12 +153,16 @@ def kmeans_fit(
 
     labels = torch.zeros(m, dtype=torch.int64, device=e.device)
     for _ in range(n_iters):
-        sims = e @ cent.T
-        labels = sims.argmax(dim=1)
-        sums = torch.zeros((n_clusters, d), dtype=torch.float64, device=e.device)
-        counts = torch.zeros(n_clusters, dtype=torch.float64, device=e.device)
-        sums.index_add_(0, labels, e.to(torch.float64))
-        counts.index_add_(0, labels, torch.ones_like(labels, dtype=torch.float64))
+        if backend == "native":
+            labels, _ = kmeans_assign(e, cent)
+            sums, counts = kmeans_accumulate(e, labels, n_clusters)
+        else:
+            sims = e @ cent.T
+            labels = sims.argmax(dim=1)
+            sums = torch.zeros((n_clusters, d), dtype=torch.float64, device=e.device)
+            counts = torch.zeros(n_clusters, dtype=torch.float64, device=e.device)
+            sums.index_add_(0, labels, e.to(torch.float64))
+            counts.index_add_(0, labels, torch.ones_like(labels, dtype=torch.float64))
         if dist is not None:  # the RCCL all-reduce (dedup_actor.py:197-232)
             dist.all_reduce(sums, group=process_group)
             dist.all_reduce(counts, group=process_group)
@@ -148,7 +231,7 @@ def semdedup(
     """
     cent, labels = kmeans_fit(
         embeddings, config.n_clusters, config.n_iters, config.random_seed,
-        process_group,
+        process_group, backend=config.kmeans_backend,
     )
     e = torch.nn.functional.normalize(embeddings.float(), dim=1, eps=1e-12)
     cos_to_cent = (e * cent[labels]).sum(dim=1)

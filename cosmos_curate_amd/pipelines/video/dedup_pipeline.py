@@ -59,6 +59,9 @@ def _setup_parser(p: argparse.ArgumentParser) -> None:
     p.add_argument("--n-iters", type=int, default=20)
     p.add_argument("--eps", type=float, default=0.01,
                    help="prune a row when max-cosine to an earlier row > 1-eps")
+    p.add_argument("--kmeans-backend", choices=["torch", "native"], default="torch",
+                   help="native: the k-means step on the HIP kernels of "
+                        "csrc/cc_kmeans.hip (d a multiple of 64 up to 1152)")
 
 
 def dedup(args: argparse.Namespace) -> dict:
@@ -74,7 +77,7 @@ def dedup(args: argparse.Namespace) -> dict:
     ids, emb = load_embeddings(pathlib.Path(args.input_embeddings_path))
     e = torch.from_numpy(emb).cuda()
     cfg = SemDedupConfig(n_clusters=args.n_clusters, n_iters=args.n_iters,
-                         eps=args.eps)
+                         eps=args.eps, kmeans_backend=args.kmeans_backend)
     t0 = time.perf_counter()
     out = semdedup(e, cfg, process_group=group)
     keep = combine_keep_masks(out["keep_mask"], group)
@@ -86,6 +89,7 @@ def dedup(args: argparse.Namespace) -> dict:
         "num_removed": int((~keep).sum().item()),
         "n_clusters": cfg.n_clusters,
         "eps": cfg.eps,
+        "kmeans_backend": cfg.kmeans_backend,
         "seconds": round(dt, 3),
         "world_size": world,
     }

@@ -698,6 +698,52 @@ int cc_tn_cls_sigmoid(const float* y, const float* w, float b, void* p,
 int cc_pairwise_max_earlier(const void* e_f32, int64_t m, int64_t d,
                             void* maxv_f32, void* argi_i32, uint64_t stream);
 
+/* One spherical k-means step (SemDedupActor.kmeans,
+ * pipelines/video/dedup/dedup_actor.py:182-313, cuML KMeansMG there): assign
+ * every row to its best centroid, then sum the rows of each cluster
+ * (DESIGN.md §24).  e [m, d] and cent [k, d] row-major f32, 16-byte aligned;
+ * d a multiple of 64 in [64, 1152], else CC_ERR_UNSUPPORTED; CC_ERR_INVALID
+ * on null or misaligned pointers, m or k < 1, k > 2^30 or a grid past 2^31-1
+ * workgroups — all before any launch.
+ *
+ * cc_kmeans_assign: labels[i] = argmax_c e_i . cent_c (int32; the smallest c
+ * among equal dot products) and, when best_f32 is not null, that dot product.
+ * Exact-f32 MFMA; no [m, k] array exists in memory.  Timed as
+ * "kmeans_assign".
+ *
+ * cc_kmeans_accumulate: sums[c] = sum over j in [offsets[c], offsets[c+1])
+ * of e[order[j]], f64 [k, d], every row of sums written (empty clusters:
+ * zeros).  order int32 [m] = the rows sorted by label (stable), offsets int32
+ * [k+1] non-decreasing; positions outside [offsets[0], offsets[k]) and row
+ * indices outside [0, m) are skipped, never dereferenced.  m <= 2^31-1.
+ * workspace: at least cc_kmeans_workspace_bytes(m, d, k) bytes, 16-byte
+ * aligned, contents irrelevant.  No floating-point atomics: the sums depend on
+ * the arguments alone, bit for bit.  Timed as "kmeans_accumulate" and
+ * "kmeans_combine". */
+typedef struct cc_kmeans_plan_info {
+  int32_t tile_rows;      /* rows of e per assign workgroup */
+  int32_t tile_cents;     /* centroids per tile */
+  int32_t cent_tiles;     /* ceil(k / tile_cents) */
+  int32_t d_chunks;       /* LDS stages per centroid tile */
+  int32_t assign_grid;    /* ceil(m / tile_rows) */
+  int32_t assign_block;
+  int32_t piece_rows;     /* sorted rows per accumulate workgroup */
+  int32_t pieces;         /* accumulate grid, ceil(m / piece_rows) */
+  int32_t acc_block;      /* d/4 threads, rounded up to whole waves */
+  int32_t combine_grid_y; /* combine grid is (k, this) */
+  int64_t workspace_bytes; /* 2 * pieces * d doubles */
+} cc_kmeans_plan_info;
+int cc_kmeans_plan(int64_t m, int64_t d, int64_t k, cc_kmeans_plan_info* out);
+/* The plan's workspace_bytes, or the negative error code. */
+int64_t cc_kmeans_workspace_bytes(int64_t m, int64_t d, int64_t k);
+int cc_kmeans_assign(const void* e_f32, int64_t m, int64_t d,
+                     const void* cent_f32, int64_t k, void* labels_i32,
+                     void* best_f32 /* may be null */, uint64_t stream);
+int cc_kmeans_accumulate(const void* e_f32, int64_t m, int64_t d,
+                         const void* order_i32, const void* offsets_i32,
+                         int64_t k, void* sums_f64, void* workspace,
+                         int64_t workspace_bytes, uint64_t stream);
+
 /* ---- kernel timing (bench.py roofline evidence) ---------------------
  * When enabled, every cc_* kernel launch is bracketed with hipEvents on
  * its launch stream; totals are accumulated per kernel name. */
