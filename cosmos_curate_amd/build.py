@@ -19,6 +19,7 @@ Per-file flags:
 - cc_kmeans.hip: cc_dedup.hip's flags plus packed-f32 instructions off, as for
   cc_attnpool.hip; the arithmetic is the f32 MFMA and ordered f64 adds, so
   contraction has nothing to contract.
+- cc_dedupseg.hip: cc_kmeans.hip's flags, for the same f32 MFMA and compares.
 """
 
 from __future__ import annotations
@@ -51,6 +52,7 @@ SOURCES: list[tuple[str, list[str]]] = [
     ("cc_tnheads.hip", [ARCH, "-ffp-contract=off"]),
     ("cc_attnpool.hip", [ARCH, *NO_PK_F32]),
     ("cc_kmeans.hip", [ARCH, *NO_PK_F32]),
+    ("cc_dedupseg.hip", [ARCH, *NO_PK_F32]),
 ]
 
 

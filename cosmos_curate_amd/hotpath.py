@@ -85,6 +85,25 @@ class KmeansPlan(ctypes.Structure):
     ]
 
 
+class PairwiseSegPlan(ctypes.Structure):
+    """cc_pairwise_seg_plan_info: how the segmented pruning scan would be
+    launched."""
+
+    _fields_ = [
+        ("tile", ctypes.c_int32),
+        ("d_chunks", ctypes.c_int32),
+        ("chunk_tiles", ctypes.c_int32),
+        ("max_chunks", ctypes.c_int32),
+        ("grid", ctypes.c_int32),
+        ("block", ctypes.c_int32),
+        ("prefix_block", ctypes.c_int32),
+        ("combine_grid", ctypes.c_int32),
+        ("combine_block", ctypes.c_int32),
+        ("prefix_bytes", ctypes.c_int64),
+        ("workspace_bytes", ctypes.c_int64),
+    ]
+
+
 def _declare(lib: ctypes.CDLL) -> None:
     c = ctypes
     lib.cc_last_error.restype = c.c_char_p
@@ -237,6 +256,14 @@ def _declare(lib: ctypes.CDLL) -> None:
     lib.cc_kmeans_accumulate.argtypes = [
         c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64,
         c.c_void_p, c.c_void_p, c.c_int64, c.c_uint64]
+    lib.cc_pairwise_seg_plan.argtypes = [
+        c.c_int64, c.c_int64, c.c_int64, c.POINTER(PairwiseSegPlan)]
+    lib.cc_pairwise_seg_workspace_bytes.argtypes = [c.c_int64, c.c_int64, c.c_int64]
+    lib.cc_pairwise_seg_workspace_bytes.restype = c.c_int64
+    lib.cc_pairwise_max_earlier_seg.argtypes = [
+        c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64,
+        c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64,
+        c.c_uint64]
     lib.cc_conv3x3_bf16.argtypes = [
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int,
         c.c_int, c.c_int, c.c_uint64]
@@ -751,6 +778,15 @@ def kmeans_plan(m: int, d: int, k: int) -> KmeansPlan:
     would reject."""
     plan = KmeansPlan()
     check(load().cc_kmeans_plan(m, d, k, ctypes.byref(plan)))
+    return plan
+
+
+def pairwise_seg_plan(m: int, d: int, k: int) -> PairwiseSegPlan:
+    """The launch plan of the segmented pruning scan over e [m, d] cut into k
+    segments (cc_pairwise_seg_plan; host-only).  Raises on shapes
+    cc_pairwise_max_earlier_seg itself would reject."""
+    plan = PairwiseSegPlan()
+    check(load().cc_pairwise_seg_plan(m, d, k, ctypes.byref(plan)))
     return plan
 
 

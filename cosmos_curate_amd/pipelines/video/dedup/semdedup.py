@@ -12,7 +12,9 @@ rebuilt MI355X-native (BASELINE config #5):
   process group init;
 - the cuPy tiled strict-upper-triangular scan (dedup :393-460) becomes
   one HIP kernel on exact-f32 MFMA (csrc/cc_dedup.hip,
-  ``cc_pairwise_max_earlier``);
+  ``cc_pairwise_max_earlier``), launched once a cluster, or with
+  ``prune_backend="segmented"`` one launch sequence over all clusters
+  (csrc/cc_dedupseg.hip, ``cc_pairwise_max_earlier_seg``);
 - "kept" semantics identical: row pruned iff max-cosine to an earlier
   (farther-from-centroid) row exceeds 1 - eps.
 
@@ -43,9 +45,11 @@ class SemDedupConfig:
     eps: float = 0.01
     random_seed: int = 0x5EED
     kmeans_backend: str = "torch"  # or "native": csrc/cc_kmeans.hip
+    prune_backend: str = "loop"  # or "segmented": csrc/cc_dedupseg.hip
 
 
 KMEANS_BACKENDS = ("torch", "native")
+PRUNE_BACKENDS = ("loop", "segmented")
 
 
 def _kmeans_operand(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -206,6 +210,90 @@ def dedup_cluster(
     return kept, maxv, argi
 
 
+def pairwise_max_earlier_segmented(
+    e: torch.Tensor,
+    order: torch.Tensor,
+    offsets: torch.Tensor,
+    *,
+    seg_first: int = 0,
+    seg_step: int = 1,
+    out: tuple[torch.Tensor, torch.Tensor] | None = None,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """The pruning scan of every segment in one launch sequence
+    (cc_pairwise_max_earlier_seg): no gathered copy of e, no host work per
+    segment, no synchronisation.
+
+    e (m, d) f32 device tensor of unit rows in their original order, d a
+    multiple of 64 in [64, 1152]; order int32 [m], scan position -> row of e;
+    offsets int32 [k+1], segment c = positions [offsets[c], offsets[c+1]).
+    Only segments c with c % seg_step == seg_first are scanned.  Returns
+    (maxv f32 [m], argi int32 [m]) indexed by scan position: the largest dot
+    product with an earlier position of the same segment and that position
+    within the segment, the smallest among equals; a segment's first position
+    gets (0.0, 0).  Positions of other segments are not written: they keep
+    what ``out`` (maxv, argi) held, or are uninitialised.  No fallback: a
+    shape the kernel refuses raises."""
+    lib = hotpath.require_gpu()
+    e = _kmeans_operand(e, "e")
+    m, d = e.shape
+    k = offsets.numel() - 1
+    for t, name, n in ((order, "order", m), (offsets, "offsets", k + 1)):
+        if (t.dtype != torch.int32 or t.shape != (n,) or t.device != e.device
+                or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous int32 [{n}] tensor on e's device")
+    ws_bytes = lib.cc_pairwise_seg_workspace_bytes(m, d, k)
+    if ws_bytes < 0:
+        hotpath.check(ws_bytes)
+    if out is None:
+        out = (torch.empty(m, dtype=torch.float32, device=e.device),
+               torch.empty(m, dtype=torch.int32, device=e.device))
+    maxv, argi = out
+    if (maxv.dtype != torch.float32 or argi.dtype != torch.int32
+            or maxv.shape != (m,) or argi.shape != (m,) or maxv.device != e.device
+            or argi.device != e.device):
+        raise ValueError("out must be (f32 [m], int32 [m]) on e's device")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=e.device)
+    stream = torch.cuda.current_stream(e.device).cuda_stream
+    hotpath.check(lib.cc_pairwise_max_earlier_seg(
+        e.data_ptr(), m, d, order.data_ptr(), offsets.data_ptr(), k, seg_first,
+        seg_step, maxv.data_ptr(), argi.data_ptr(), ws.data_ptr(), ws_bytes,
+        stream))
+    return maxv, argi
+
+
+def prune_clusters(
+    e: torch.Tensor,
+    labels: torch.Tensor,
+    dist_to_cent: torch.Tensor,
+    k: int,
+    eps: float,
+    rank: int = 0,
+    world: int = 1,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """The pruning pass over all clusters c with c % world == rank at once.
+
+    The scan order is the per-cluster loop's: inside a cluster, farthest from
+    the centroid first, equal distances in row order (two stable sorts, by
+    distance descending then by label), and ``searchsorted`` finds the
+    clusters' offsets: torch integer plumbing that never synchronises with
+    the host.  e (m, d) unit rows on the device.  Returns (keep bool [m] in row
+    order, True for rows of clusters this rank does not own; counts int64 [2] =
+    kept and total rows of the owned clusters, still on the device)."""
+    by_dist = torch.argsort(dist_to_cent, descending=True, stable=True)
+    sorted_labels, by_label = torch.sort(labels[by_dist], stable=True)
+    order = by_dist[by_label]
+    offsets = torch.searchsorted(
+        sorted_labels, torch.arange(k + 1, dtype=labels.dtype, device=e.device))
+    maxv, _ = pairwise_max_earlier_segmented(
+        e, order.to(torch.int32), offsets.to(torch.int32),
+        seg_first=rank, seg_step=world)
+    owned = sorted_labels % world == rank
+    kept = (maxv <= (1.0 - eps)) & owned  # maxv is uninitialised elsewhere
+    keep = torch.empty(len(e), dtype=torch.bool, device=e.device)
+    keep[order] = kept | ~owned
+    return keep, torch.stack([kept.sum(), owned.sum()])
+
+
 def combine_keep_masks(keep: torch.Tensor, process_group=None) -> torch.Tensor:
     """AND the per-rank keep masks (each rank pruned only the clusters it
     owns, leaving the rest True) — the dedup_pipeline.py N>1 combine,
@@ -228,7 +316,14 @@ def semdedup(
     Clusters are processed round-robin by rank (dedup_pipeline.py:237-300
     assigns cluster ranges to actors).  Returns counts + per-row keep mask
     aligned with the input order.
+
+    ``config.prune_backend="segmented"`` prunes all of the rank's clusters in
+    one launch sequence (prune_clusters) and synchronises once, for the two
+    counts; ``"loop"`` launches the scan once a cluster.
     """
+    if config.prune_backend not in PRUNE_BACKENDS:
+        raise ValueError(
+            f"prune_backend must be one of {PRUNE_BACKENDS}, got {config.prune_backend!r}")
     cent, labels = kmeans_fit(
         embeddings, config.n_clusters, config.n_iters, config.random_seed,
         process_group, backend=config.kmeans_backend,
@@ -240,6 +335,11 @@ def semdedup(
     keep = torch.ones(len(e), dtype=torch.bool, device=e.device)
     rank = torch.distributed.get_rank(process_group) if process_group else 0
     world = torch.distributed.get_world_size(process_group) if process_group else 1
+    if config.prune_backend == "segmented":
+        keep, counts = prune_clusters(
+            e, labels, dist_to_cent, config.n_clusters, config.eps, rank, world)
+        kept_n, total_n = counts.tolist()
+        return {"kept": kept_n, "total": total_n, "keep_mask": keep, "labels": labels}
     kept_n = 0
     total_n = 0
     for cid in range(rank, config.n_clusters, world):

@@ -62,6 +62,9 @@ def _setup_parser(p: argparse.ArgumentParser) -> None:
     p.add_argument("--kmeans-backend", choices=["torch", "native"], default="torch",
                    help="native: the k-means step on the HIP kernels of "
                         "csrc/cc_kmeans.hip (d a multiple of 64 up to 1152)")
+    p.add_argument("--prune-backend", choices=["loop", "segmented"], default="loop",
+                   help="segmented: all clusters pruned in one launch sequence "
+                        "on csrc/cc_dedupseg.hip (d a multiple of 64 up to 1152)")
 
 
 def dedup(args: argparse.Namespace) -> dict:
@@ -77,7 +80,8 @@ def dedup(args: argparse.Namespace) -> dict:
     ids, emb = load_embeddings(pathlib.Path(args.input_embeddings_path))
     e = torch.from_numpy(emb).cuda()
     cfg = SemDedupConfig(n_clusters=args.n_clusters, n_iters=args.n_iters,
-                         eps=args.eps, kmeans_backend=args.kmeans_backend)
+                         eps=args.eps, kmeans_backend=args.kmeans_backend,
+                         prune_backend=args.prune_backend)
     t0 = time.perf_counter()
     out = semdedup(e, cfg, process_group=group)
     keep = combine_keep_masks(out["keep_mask"], group)
@@ -90,6 +94,7 @@ def dedup(args: argparse.Namespace) -> dict:
         "n_clusters": cfg.n_clusters,
         "eps": cfg.eps,
         "kmeans_backend": cfg.kmeans_backend,
+        "prune_backend": cfg.prune_backend,
         "seconds": round(dt, 3),
         "world_size": world,
     }

@@ -744,6 +744,49 @@ int cc_kmeans_accumulate(const void* e_f32, int64_t m, int64_t d,
                          int64_t k, void* sums_f64, void* workspace,
                          int64_t workspace_bytes, uint64_t stream);
 
+/* The pruning scan of every dedup cluster in one launch sequence (DESIGN.md
+ * §25): cc_pairwise_max_earlier over the segments of a labelled set, without
+ * a gathered copy of e and without host work per segment.  e [m, d] row-major
+ * f32 unit rows in their original order, 16-byte aligned, d a multiple of 64
+ * in [64, 1152] (else CC_ERR_UNSUPPORTED); order int32 [m], scan position ->
+ * row of e; offsets int32 [k+1], segment c = scan positions [offsets[c],
+ * offsets[c+1]), empty segments allowed.  Only segments c with
+ * c % seg_step == seg_first are processed.  Per scan position p of such a
+ * segment: maxv[p] = the largest dot product with a row at an earlier position
+ * of the same segment, argi[p] = that row's segment-local position (the
+ * smallest among equal dot products); a segment's first position gets
+ * (0.0, 0).  Positions of other segments are not written.  Offsets are
+ * clamped to [0, m] and order values outside [0, m) are staged as zero rows,
+ * never dereferenced.  CC_ERR_INVALID on null or misaligned pointers, m or k
+ * < 1, m > 2^31-1, k > 2^30, seg_step < 1, seg_first outside [0, seg_step) or
+ * a workspace below cc_pairwise_seg_workspace_bytes(m, d, k) (16-byte aligned,
+ * contents irrelevant) — all before any launch.  Exact-f32 MFMA, no
+ * floating-point atomics: the outputs depend on the arguments alone, bit for
+ * bit.  Timed as "pairwise_seg_prefix", "pairwise_seg" and
+ * "pairwise_seg_combine". */
+typedef struct cc_pairwise_seg_plan_info {
+  int32_t tile;           /* scan positions per j-tile and per i-tile */
+  int32_t d_chunks;       /* LDS stages per tile pair */
+  int32_t chunk_tiles;    /* C: i-tiles a work item covers at most */
+  int32_t max_chunks;     /* work items a j-tile is cut into at most */
+  int32_t grid;           /* persistent workgroups walking the work list */
+  int32_t block;
+  int32_t prefix_block;   /* the work-list prologue is one workgroup */
+  int32_t combine_grid;   /* ceil(m / combine_block) */
+  int32_t combine_block;
+  int64_t prefix_bytes;   /* work-list prefix, (k + 1) int64, 16-byte padded */
+  int64_t workspace_bytes; /* prefix, then (value, index) partials */
+} cc_pairwise_seg_plan_info;
+int cc_pairwise_seg_plan(int64_t m, int64_t d, int64_t k,
+                         cc_pairwise_seg_plan_info* out);
+/* The plan's workspace_bytes, or the negative error code. */
+int64_t cc_pairwise_seg_workspace_bytes(int64_t m, int64_t d, int64_t k);
+int cc_pairwise_max_earlier_seg(const void* e_f32, int64_t m, int64_t d,
+                                const void* order_i32, const void* offsets_i32,
+                                int64_t k, int64_t seg_first, int64_t seg_step,
+                                void* maxv_f32, void* argi_i32, void* workspace,
+                                int64_t workspace_bytes, uint64_t stream);
+
 /* ---- kernel timing (bench.py roofline evidence) ---------------------
  * When enabled, every cc_* kernel launch is bracketed with hipEvents on
  * its launch stream; totals are accumulated per kernel name. */
