@@ -37,8 +37,9 @@
 // small and the strided launches.
 //
 // k_gemm_bf16_t256 (256² body): 256x256 block tile, 512 threads = 8 waves
-// (2x4), each wave 128x64; 8-phase schedule with counted vmcnt waits, a
-// persistent fleet of workgroups walking the tile list, and an LDS-staged
+// (2x4), each wave 128x64; a ping-pong K-loop (the two waves of a SIMD
+// alternate between a memory and an MFMA cluster) with counted vmcnt waits,
+// a persistent fleet of workgroups walking the tile list, and an LDS-staged
 // coalesced bf16 epilogue for fused launches.  Dense operands, K % 128 ==
 // 0 and K >= 256 only.  Runs every large ViT GEMM (details at the kernel).
 
@@ -284,14 +285,14 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
 #undef BS
 }
 
-// ---- 256x256 8-phase template kernel (guide "The 256² 8-phase
-// template", schedule derived + race-screened through tools/gemm_v10
-// ... v22; round-2 ladder in DESIGN.md §9a) ----
+// ---- 256x256 template kernel (round-2 ladder in DESIGN.md §9a, the
+// K-loop's schedule in §26) ----
 // 512 threads = 8 waves (2M x 4N), per-wave 128x64 = 8x4 frags; LDS
-// 128 KiB; PERSISTENT fleet (grid = min(nwg, 256)); raw s_barrier
-// phases; COUNTED vmcnt(4) publish before the last barrier of each K-tile
-// (B(t+2) spans each boundary in flight); T19 scheduler weave of next-phase ds_reads into
-// the MFMA clusters; template-selected epilogue (LDS-staged coalesced
+// 128 KiB; PERSISTENT fleet (grid = min(nwg, 256)); a K-tile is 4 memory
+// and 4 MFMA clusters per wave, raw s_barrier between them, the two wave
+// groups one cluster apart; COUNTED vmcnt(4) publish in the last memory
+// cluster of each K-tile (B(t+2) spans each boundary in flight);
+// template-selected epilogue (LDS-staged coalesced
 // for fused bias/act/residual, scalar otherwise; EPI_STAGED is always
 // ACT != 0 || HAS_BIAS || HAS_RES).  Which shapes it serves is
 // cc::gemm_plan's rule (the ViT GEMM mix; batch-64 per-shape TF in
@@ -386,6 +387,30 @@ __device__ __forceinline__ float sum8(float v) {
   return dpp_add<0x141>(dpp_add<0x4e>(dpp_add<0xb1>(v)));
 }
 
+// CC_GEMM_STAMPS (tools/gemm_stamps.py builds a library of its own with it;
+// the production build never sets it): every tile records the 100 MHz wall
+// clock at its rep top, at the three barriers that bound the first two
+// phases of its first K-tile, at the end of its K-loop and at the end of its
+// epilogue, CC_GEMM_STAMP_N values at stamps[tile id * CC_GEMM_STAMP_N].
+// The clock is read by every wave (a scalar instruction) and stored by one
+// lane of the workgroup, after the pre-epilogue barrier: there the stores
+// are older than every load and store the epilogue's hand-counted waits
+// count, and an older entry in the queue changes none of them.  The
+// epilogue-end stamp of a tile is stored with the next tile's, or after the
+// loop.
+#ifdef CC_GEMM_STAMPS
+#define CC_GEMM_STAMP_N 6
+__device__ unsigned long long* cc_gemm_stamp_buf;
+#define CC_STAMP(i) (stamp[i] = wall_clock64())
+#define CC_STAMP_IF(cond, i) \
+  do {                       \
+    if (cond) CC_STAMP(i);   \
+  } while (0)
+#else
+#define CC_STAMP(i) ((void)0)
+#define CC_STAMP_IF(cond, i) ((void)0)
+#endif
+
 template <int ACT, bool HAS_BIAS, bool HAS_RES, bool EPI_STAGED, bool LN_IN,
           bool STATS>
 __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
@@ -397,7 +422,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
     float2* __restrict__ stats) {
   static_assert(!STATS || HAS_RES, "the stats epilogue is the residual one");
   // Round-2 structure: PERSISTENT multi-tile (grid = min(nwg, 256), one
-  // WG per CU) around the round-1 8-phase glds schedule.  Each WG walks
+  // WG per CU) around the glds K-loop.  Each WG walks
   // tiles bid, bid+grid, ... and issues the NEXT tile's 12-glds
   // prologue BEFORE the epilogue stores, so prologue HBM latency hides
   // under the C writeback instead of stalling a fresh WG (it does only
@@ -407,8 +432,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
   // (profiles/r02_gemm_persist.log: fc1 711->874, fc2 795->968, patch
   // 814->964, qkv 724->887 TF within one box).  order_mode: 0 = plain
   // stride; 1 = stride + bijective XCD remap (skinny-N grids, L2 row
-  // sharing).  Sync structure per K-tile is UNCHANGED from the
-  // race-screened v11 (vmcnt(0) publish at ph3, leading barriers).
+  // sharing).
   static_assert(!LN_IN || HAS_BIAS, "the folded norm always carries a bias");
   // a launch with a bias stages the column tables, whichever epilogue its
   // output type then takes
@@ -456,6 +480,9 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
   const int lane = tid & 63;
   const int wid = tid >> 6;
   const int waveM = wid >> 2, waveN = wid & 3;
+  // the wave group (= waveM) as a scalar: it decides who takes the two
+  // barriers that open and close the K-loop's stagger
+  const int grp = __builtin_amdgcn_readfirstlane(wid) >> 2;
   const long KT = K / BK;  // the plan guarantees even, >= 4
   const long srow = wid * 16;
   const int arow_base = waveM * WM2 + (lane & 15);
@@ -470,6 +497,14 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
 #define STAGE_B2(t, h)                                                      \
   stage_rows<2>(B, K, bn + (h) * 128 + srow, N, (t) * BK,                   \
                 B2T((t) & 1) + ((h) * 128 + srow) * BK, lane)
+// In the K-loop a wave stages rows of the A half its own wave group reads
+// (group waveM reads rows [128 waveM, 128 waveM + 128) and nothing else):
+// rows [32 wid, 32 wid + 32), 4 glds.  The same 4 glds per wave and K-tile
+// as two STAGE_A2, so no vmcnt count depends on which of the two is used;
+// the prologues keep STAGE_A2.
+#define STAGE_A2_OWN(t)                                                     \
+  stage_rows<4>(A, K, bm + 2 * srow, M, (t) * BK,                           \
+                A2T((t) & 1) + 2 * srow * BK, lane)
 
   const int tiles = (nwg + (int)gridDim.x - 1) / (int)gridDim.x;
   long bm, bn;
@@ -499,6 +534,10 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
   constexpr int PASS_STORES = STATS ? 8 : 4;
   const bool staged = (c_is_bf16 && EPI_STAGED) || LN_IN || STATS;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the first prologue
+#ifdef CC_GEMM_STAMPS
+  unsigned long long stamp[CC_GEMM_STAMP_N] = {};
+  long stamp_tile = -1;  // the tile whose epilogue-end stamp is not stored yet
+#endif
 
   for (int rep = 0; rep < tiles; rep++) {
     if ((int)blockIdx.x + rep * (int)gridDim.x >= nwg) break;
@@ -524,26 +563,85 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();
+    CC_STAMP(0);
 
+// ---- the K-loop: a ping-pong between the two wave groups
+//
+// Waves wid and wid + 4 run on one SIMD (measured: with the groups cut the
+// other way, by wid & 1, the same loop is 12 % slower than the lockstep one
+// it replaces).  They are group 0 (waveM 0) and group 1 (waveM 1).  Every
+// wave runs the same code per K-tile,
+//     M0 | C0 | M1 | C1 | M2 | C2 | M3 | C3        ("|" = SYNC2)
+// a memory cluster Mq (the ds_reads of quadrant q's fragments, glds issues,
+// in M3 the counted wait) and a compute cluster Cq (16 MFMAs).  Group 1
+// takes one extra SYNC2 on the way in and group 0 one on the way out, so
+// all waves execute the same number of barriers, 8 KT per tile, and group 1
+// runs exactly one cluster behind group 0: whenever one wave of a SIMD is
+// in a memory cluster the other is in a compute cluster.  Number the
+// barrier intervals of a tile 0, 1, ...: group 0 runs cluster k of the tile
+// (M0 = 0, C0 = 1, ..., C3 of K-tile t = 8 t + 7) in interval k, group 1 in
+// interval k + 1.  "A barrier between X and Y" below means: X is in an
+// earlier interval than Y.  Outside the loop (rep-top barrier and before,
+// pre-epilogue barrier and after) all waves are at the same program point,
+// as ever, so the epilogue, the prologues, the tables and their waits are
+// untouched by this.
+//
+// Hazards, per LDS region.  Rule (§14): counted wait by the writer, then a
+// barrier, then the first read; and last read COMPLETE (lgkmcnt(0), the
+// first instruction of every compute cluster), then a barrier, then the
+// overwrite's issue.
+//
+// A-buf (t+1)&1, half h.  Written and read by group h only (STAGE_A2_OWN;
+//   a wave's fragments come from rows [128 waveM, +128)), and the four
+//   waves of a group are at the same program point, so the stagger does not
+//   enter: this is a 4-wave lockstep argument.
+//   write: glds A(t+1) issued in M0(t) by the group's waves.
+//   wait -> read: vmcnt in M3(t) (each wave, its own loads) | SYNC2 | C3 |
+//     SYNC2 | first read in M0(t+1).
+//   last read -> overwrite: the buffer held A(t-1); its last reads are
+//     issued in M3(t-1) and complete at the top of C3(t-1) | SYNC2 | M0(t).
+// B-buf t&1, both halves.  Written by all 8 waves (16 rows of each half
+//   each), read by both groups (READ_B2 in M0).
+//   write: glds B(t+2) h0 in M2(t), h1 in M3(t): intervals 8t+4, 8t+6 for
+//     group 0 and 8t+5, 8t+7 for group 1.
+//   wait -> read: vmcnt in M3(t+1) (intervals 8t+14 / 8t+15; B(t+2) is
+//     older than the 4 loads that wait lets stand) | the SYNC2 that ends
+//     interval 8t+15 | first read in M0(t+2), interval 8t+16 (group 0).
+//   last read -> overwrite: the buffer held B(t); group 1 issues its reads
+//     in interval 8t+1 and they are complete at the top of its C0, inside
+//     interval 8t+2 | the SYNC2 that ends 8t+2 | earliest overwrite issue,
+//     group 0's M2(t), interval 8t+4.  (M1(t), interval 8t+2, would NOT be
+//     safe for group 0, which is why B is not staged earlier.)
+// A-buf1 as the epilogue's staging area.  Written (ds_write) and read back
+//   by each wave in its own 4 KB slice, rows [32 wid, +32), after the
+//   pre-epilogue barrier, which every wave reaches after its last C3, so
+//   with every fragment read complete.  The next tile's first glds into
+//   A-buf1 is STAGE_A2_OWN(1) in M0(0), behind the rep-top barrier and every
+//   wave's last slice read; it even writes the issuing wave's own slice.
+// The (mean, rstd) and column tables are written by the prologues and read
+//   by the epilogue, both outside the staggered span.
+//
+// vmcnt counts.  Per wave and K-tile the glds issue order is A(t+1):4 in M0,
+// B(t+2)h0:2 in M2, B(t+2)h1:2 in M3, the same counts and the same relative
+// order (A before B) as the lockstep loop had, so its waits carry over:
+// M3's queue, newest first, is [B(t+2):4, A(t+1):4, <older>] -> vmcnt(4).
+
+// SYNC2: the barrier between two clusters.  Nothing is scheduled across it
+// (s_barrier alone orders memory instructions only; the MFMAs are not), so
+// a cluster holds exactly what the source puts in it.
+#define SYNC2()                                                             \
+  do {                                                                      \
+    __builtin_amdgcn_sched_barrier(0);                                      \
+    __builtin_amdgcn_s_barrier();                                           \
+    __builtin_amdgcn_sched_barrier(0);                                      \
+  } while (0)
+
+// compute cluster q: the 16 MFMAs of M-fragments 2q, 2q+1, on the fragments
+// the memory cluster before it read (same MFMAs, same order per accumulator
+// as ever: C is bit-identical whatever the schedule around them)
 #define PHASE_MFMA2(q)                                                      \
   do {                                                                      \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                      \
-    /* T19 dictation (round 2, +1-3%/shape, profiles/r02_gemm_v21.log):  */ \
-    /* weave the next phase's ds_reads and the glds issues between the   */ \
-    /* 16 MFMAs so their latency hides under the cluster (the source-    */ \
-    /* level version of this, v12, regressed; the compile-time directive */ \
-    /* does it without perturbing issue order elsewhere).  setprio       */ \
-    /* dropped: it fenced the scheduler out of exactly this interleave.  */ \
-    /* pattern 3 of the sweep (profiles/r02_t19_sweep.log): lead with   */ \
-    /* 2 MFMAs, then weave [dsr, 2 MFMA, vmem] x6 — best at every ViT   */ \
-    /* shape (patch 1041, qkv 916, fc1 914, fc2 1056 TF vs 875-1009     */ \
-    /* for the coarser patterns).                                       */ \
-    __builtin_amdgcn_sched_group_barrier(0x8 /*MFMA*/, 2, 0);               \
-    _Pragma("unroll") for (int gi = 0; gi < 6; gi++) {                      \
-      __builtin_amdgcn_sched_group_barrier(0x100 /*DS_READ*/, 1, 0);        \
-      __builtin_amdgcn_sched_group_barrier(0x8 /*MFMA*/, 2, 0);             \
-      __builtin_amdgcn_sched_group_barrier(0x10 /*VMEM*/, 1, 0);            \
-    }                                                                       \
     _Pragma("unroll") for (int g = 0; g < 2; g++) {                         \
       _Pragma("unroll") for (int m = 0; m < 2; m++) {                       \
         _Pragma("unroll") for (int n = 0; n < NFR2; n++) {                  \
@@ -553,13 +651,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
       }                                                                     \
     }                                                                       \
   } while (0)
-  /* NOTE: no trailing barrier per phase (v11, profiles/r01_v11_ab.log,
-     +5-8%): the B-buffer write-after-read hazard needs only 2-phase
-     separation, which the per-phase leading barrier provides — wave W
-     drains its reads (lgkm0) before it reaches the NEXT phase's
-     barrier, and any other wave's conflicting glds issues only after
-     passing that barrier, two phases later.  Race-screened +
-     determinism-checked at 774-3156-block grids. */
 
 #define READ_A2(At, q)                                                      \
   _Pragma("unroll") for (int g = 0; g < 2; g++) {                           \
@@ -575,76 +666,93 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
         frag_read(Bt, brow_base + n * FRAG, k16);                           \
   }
 
-// one K-tile = 4 phases; stages the next A halves in ph1-2 and the
-// tile-after-next B halves in ph3-4 (issue order proves vmcnt(4)):
+// one K-tile = 4 memory clusters M0-M3 and 4 compute clusters C0-C3,
+// alternating, a SYNC2 after each (none after the last C3 of the loop).
+// Where the glds sit is measured: all of A(t+1) in M0, the
+// earliest its buffer is free, and B(t+2) split over M2 and M3; with A in
+// M0 + M1 and B in M3 the same loop was no faster than the lockstep one.
 #define KTILE2(t)                                                           \
   do {                                                                      \
     const __bf16* At = A2T((t) & 1);                                        \
     const __bf16* Bt = B2T((t) & 1);                                        \
-    /* no-op since the publish below moved back before the barrier (the */ \
-    /* queue holds only B(t+1):4 here, or nothing at tile 0 of a rep);  */ \
-    /* kept as the compiler fence the measured schedule was built with. */ \
-    /* At tile 0 of a later rep the queue holds the previous epilogue's */ \
-    /* stores instead, which nothing here depends on: the count lets    */ \
-    /* them all stand, so they retire at the publish below              */ \
+    /* M0.  The wait is a no-op (the queue holds only B(t+1):4 here, or  */ \
+    /* nothing at tile 0 of a rep), kept as a compiler fence.  At tile 0 */ \
+    /* of a later rep the queue holds the previous epilogue's stores     */ \
+    /* instead, which nothing here depends on: the count lets them all   */ \
+    /* stand, so they retire at the publish below                        */ \
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 + 4 * PASS_STORES)           \
                  : "memory");                                               \
     READ_B2(Bt);                                                            \
     READ_A2(At, 0);                                                         \
-    if ((t) + 1 < KT) STAGE_A2((t) + 1, 0);                                 \
-    __builtin_amdgcn_s_barrier();                                           \
+    if ((t) + 1 < KT) STAGE_A2_OWN((t) + 1);                                \
+    SYNC2();                                                                \
+    CC_STAMP_IF((t) == 0, 1);                                               \
     PHASE_MFMA2(0);                                                         \
-    READ_A2(At, 1);                                                         \
-    if ((t) + 1 < KT) STAGE_A2((t) + 1, 1);                                 \
-    __builtin_amdgcn_s_barrier();                                           \
+    SYNC2();                                                                \
+    READ_A2(At, 1); /* M1 */                                                \
+    SYNC2();                                                                \
+    CC_STAMP_IF((t) == 0, 2);                                               \
     PHASE_MFMA2(1);                                                         \
-    READ_A2(At, 2);                                                         \
-    __builtin_amdgcn_s_barrier();                                           \
+    SYNC2();                                                                \
+    READ_A2(At, 2); /* M2 */                                                \
+    if ((t) + 2 < KT) STAGE_B2((t) + 2, 0);                                 \
+    SYNC2();                                                                \
+    CC_STAMP_IF((t) == 0, 3);                                               \
     PHASE_MFMA2(2);                                                         \
-    READ_A2(At, 3);                                                         \
-    /* COUNTED publish (round 2, replaces the per-tile vmcnt(0) drain):  */ \
-    /* the next tile's LDS reads need A(t+1) [ph1-2, 4 loads/wave] and   */ \
-    /* B(t+1) [issued one tile earlier, strictly older] landed.  After   */ \
-    /* issuing B(t+2)'s 4 loads, the per-wave VMEM queue newest-first is */ \
-    /* [B(t+2):4, A(t+1):4, <older>]; vmcnt(4) retires everything except */ \
-    /* B(t+2), which keeps spanning the tile boundary.  r01's            */ \
-    /* "nondeterministic counted wait" (profiles/r01_t256_det2.log) sat  */ \
-    /* BEFORE the B(t+2) issues with exactly 4 loads outstanding — a     */ \
-    /* no-op wait, not out-of-order retirement; this placement fixes the */ \
-    /* count.  Verified: 6-run multi-shape determinism screen + full GPU */ \
-    /* parity suite (profiles/r02_gemm_v19.log).  Measured: fc1 864->905,*/ \
-    /* fc2 950->1023, patch 940->1004 TF within one box.                 */ \
+    SYNC2();                                                                \
+    READ_A2(At, 3); /* M3 */                                                \
+    /* COUNTED publish: the next tile's LDS reads need A(t+1) [M0: 4     */ \
+    /* loads per wave] and B(t+1) [issued one tile earlier, strictly     */ \
+    /* older] landed.  After issuing B(t+2)'s 4 loads, the per-wave VMEM */ \
+    /* queue newest-first is [B(t+2):4, A(t+1):4, <older>]; vmcnt(4)     */ \
+    /* retires everything except B(t+2), which keeps spanning the tile   */ \
+    /* boundary.  The wait sits in the memory cluster: while this wave   */ \
+    /* waits for memory, the other group's wave on its SIMD multiplies.  */ \
     if ((t) + 2 < KT) {                                                     \
-      STAGE_B2((t) + 2, 0);                                                 \
       STAGE_B2((t) + 2, 1);                                                 \
-      /* The wait sits HERE, before the barrier.  For a while it sat at  */ \
-      /* the next tile's top (one more MFMA cluster of latency cover):   */ \
-      /* that retires only the waiting wave's own loads, and the reads   */ \
-      /* right after it take rows other waves staged, with no barrier    */ \
-      /* after THEIR wait - a late load was read stale.  Dormant until   */ \
-      /* the folded-LN route changed the memory traffic around the GEMMs */ \
-      /* (1-7 of 224 bench rows off by ~1e-4 in 6 of 6 runs; 0 of 6 with */ \
-      /* the wait here, profiles/r04_lnfold_det.txt).  Rule: counted     */ \
-      /* wait, then a barrier, then the first read*/ \
+      /* The wait sits HERE, before the barrier, not at the next tile's  */ \
+      /* top: a wait retires only the waiting wave's own loads, and the  */ \
+      /* reads of the next tile take rows other waves staged (a late     */ \
+      /* load was read stale, profiles/r04_lnfold_det.txt).  Rule:       */ \
+      /* counted wait, then a barrier, then the first read (DESIGN.md    */ \
+      /* sections 14 and 26)                                             */ \
       asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                      \
     } else {                                                                \
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* tail drain */     \
     }                                                                       \
-    __builtin_amdgcn_s_barrier();                                           \
+    SYNC2();                                                                \
     PHASE_MFMA2(3);                                                         \
+    if ((t) + 1 < KT) SYNC2();                                              \
   } while (0)
 
+    // Open the stagger: group 1 takes one barrier more on the way in, so it
+    // runs one cluster behind group 0 from here to the end of the K-loop.
+    if (grp == 1) SYNC2();
     for (long it = 0; it < KT / 2; ++it) {
       KTILE2(2 * it);
       KTILE2(2 * it + 1);
     }
+    // Close it: group 0 takes the barrier group 1 took on the way in (it
+    // pairs with the one group 1 passes in front of its last C3), so every
+    // wave has executed 8 KT barriers and meets the others at the next one.
+    if (grp == 0) SYNC2();
 
     const long ebm = bm, ebn = bn;
     // barrier before the epilogue: the bf16 epilogue below stages C
     // through A-buf1, whose rows 96-127/224-255 other waves were still
-    // reading in the last phase; the next tile's prologue (further
-    // below) overwrites A-buf0/B-bufs with the same hazard.
+    // reading in their last M3; the next tile's prologue (further
+    // below) overwrites A-buf0/B-bufs with the same hazard.  Both groups
+    // arrive from their last C3 (group 0 by way of the closing SYNC2).
     __builtin_amdgcn_s_barrier();
+#ifdef CC_GEMM_STAMPS
+    CC_STAMP(4);
+    if (tid == 0 && cc_gemm_stamp_buf) {
+      unsigned long long* s = cc_gemm_stamp_buf;
+      if (stamp_tile >= 0) s[stamp_tile * CC_GEMM_STAMP_N + 5] = stamp[5];
+      stamp_tile = (long)blockIdx.x + (long)rep * (long)gridDim.x;
+      for (int i = 0; i < 5; i++) s[stamp_tile * CC_GEMM_STAMP_N + i] = stamp[i];
+    }
+#endif
     // From here to the end of the tile every lane-dependent value is
     // derived again from an opaque copy of the thread id.  Derived from
     // `tid` itself, the address parts the epilogue and the next prologue
@@ -907,7 +1015,12 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
       }
     }
     }  // lane-dependent values of the epilogue
+    CC_STAMP(5);
   }
+#ifdef CC_GEMM_STAMPS
+  if (tid == 0 && stamp_tile >= 0)
+    cc_gemm_stamp_buf[stamp_tile * CC_GEMM_STAMP_N + 5] = stamp[5];
+#endif
 #undef LNTAB
 #undef STAGE_LN2
 #undef COLTAB_AT
@@ -915,7 +1028,9 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
 #undef A2T
 #undef B2T
 #undef STAGE_A2
+#undef STAGE_A2_OWN
 #undef STAGE_B2
+#undef SYNC2
 #undef PHASE_MFMA2
 #undef READ_A2
 #undef READ_B2
@@ -1118,3 +1233,18 @@ extern "C" int cc_gemm_bf16_rms(const void* A, int64_t row_step,
   return gemm_norm_in(true, A, row_step, stats, murstd, Wfold, colsum, cbias,
                       C, M, N, K, act, eps, stream);
 }
+
+#ifdef CC_GEMM_STAMPS
+// points the stamped kernels at `buf` (CC_GEMM_STAMP_N values per tile of the
+// launches that follow); returns the wall clock's rate in kHz, or -1
+extern "C" int cc_gemm_stamps_set(void* buf) {
+  unsigned long long* p = (unsigned long long*)buf;
+  int khz = 0;
+  if (hipMemcpyToSymbol(HIP_SYMBOL(cc_gemm_stamp_buf), &p, sizeof(p)) !=
+          hipSuccess ||
+      hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, 0) !=
+          hipSuccess)
+    return -1;
+  return khz;
+}
+#endif

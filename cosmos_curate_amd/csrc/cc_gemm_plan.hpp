@@ -76,7 +76,7 @@ inline int gemm_plan(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldr,
   // is a single row of 128² tiles.
   const bool t256_ok =
       (K % 128 == 0) && (K >= 256) && M > GEMM_T256 / 2;
-  // 256² 8-phase body for the shapes its halved A/B re-read traffic pays
+  // 256² body for the shapes its halved A/B re-read traffic pays
   // on: K >= 1536 or N >= 1536 (profiles/r01_v10_b64.log), and, since it
   // became persistent, every shape whose 256-tile grid fills the fleet —
   // that includes N = 768 && K = 768 at large M (out64 720 -> 796 TF,
