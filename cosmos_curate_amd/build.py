@@ -8,7 +8,9 @@ Per-file flags:
 - cc_pixel.hip: -ffp-contract=off — the pixel kernels promise bit-exact f32
   arithmetic vs the numpy oracle (oracle/color.py); FMA contraction would
   change rounding.
-- cc_gemm.hip: default contraction (MFMA does the math anyway).
+- cc_gemm.hip: default contraction (MFMA does the math anyway), packed-f32
+  instructions off: the 256² epilogue works on adjacent register pairs, which
+  hipcc would otherwise turn into v_pk_mul_f32 / v_pk_fma_f32 by the thousand.
 - cc_motion.hip: integer arithmetic only; no floating-point flags matter.
 - cc_conv.hip: default contraction (MFMA, and an FMA first layer whose
   tolerance is the f32 accumulation bound, not bit-exactness).
@@ -43,7 +45,7 @@ SOURCES: list[tuple[str, list[str]]] = [
     ("cc_demux.cpp", []),
     ("cc_decode.cpp", []),
     ("cc_pixel.hip", [ARCH, "-ffp-contract=off"]),
-    ("cc_gemm.hip", [ARCH]),
+    ("cc_gemm.hip", [ARCH, *NO_PK_F32]),
     ("cc_dedup.hip", [ARCH]),
     ("cc_ln.hip", [ARCH]),
     ("cc_attn.hip", [ARCH]),

@@ -69,6 +69,19 @@ __device__ __forceinline__ unsigned short f32_to_bf16_rne(float v) {
   return (unsigned short)((cv.u + 0x7fffu + lsb) >> 16);
 }
 
+// Two f32 -> two bf16 in one dword (lo in the low half), the 256² body's
+// rounding: v_cvt_pk_bf16_f32 on gfx950, one instruction per pair.  It and
+// f32_to_bf16_rne give the same bits for every finite value (round to nearest
+// even, overflow to infinity) and for infinities; they may differ on NaN,
+// where the hardware quiets the payload and the integer form adds into it.
+// The 128² body keeps the integer form.
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+__device__ __forceinline__ unsigned int f32x2_to_bf16x2(float lo, float hi) {
+  const f32x2 f = {lo, hi};
+  return __builtin_bit_cast(unsigned int, __builtin_convertvector(f, bf16x2));
+}
+
 // fused activations (quick-gelu / SigLIP tanh-gelu / InternVideo2 erf-gelu;
 // see epilogue notes)
 template <int ACT>
@@ -286,8 +299,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(
 }
 
 // ---- 256x256 template kernel (round-2 ladder in DESIGN.md §9a, the
-// K-loop's schedule in §26) ----
-// 512 threads = 8 waves (2M x 4N), per-wave 128x64 = 8x4 frags; LDS
+// K-loop's schedule in §26, the transposed accumulators in §27) ----
+// 512 threads = 8 waves (2M x 4N), per-wave 128x64 = 8x4 frags, each
+// computed TRANSPOSED (the B fragment is the MFMA's first operand): lane l,
+// register r of fragment (m, n) is C row 16 m + (l & 15), column 16 n +
+// 4 (l >> 4) + r, so a lane owns four adjacent columns, rounds them with two
+// v_cvt_pk_bf16_f32 and writes them with one 8-byte LDS or global store; LDS
 // 128 KiB; PERSISTENT fleet (grid = min(nwg, 256)); a K-tile is 4 memory
 // and 4 MFMA clusters per wave, raw s_barrier between them, the two wave
 // groups one cluster apart; COUNTED vmcnt(4) publish in the last memory
@@ -390,25 +407,36 @@ __device__ __forceinline__ float sum8(float v) {
 // CC_GEMM_STAMPS (tools/gemm_stamps.py builds a library of its own with it;
 // the production build never sets it): every tile records the 100 MHz wall
 // clock at its rep top, at the three barriers that bound the first two
-// phases of its first K-tile, at the end of its K-loop and at the end of its
-// epilogue, CC_GEMM_STAMP_N values at stamps[tile id * CC_GEMM_STAMP_N].
+// phases of its first K-tile, at the end of its K-loop, at the end of its
+// epilogue (5) and, in the staged epilogue, at the end of each pass's write
+// phase (6 + p) and of its read-back and store issue (10 + p), CC_GEMM_STAMP_N
+// values at stamps[tile id * CC_GEMM_STAMP_N].  The stamps inside the
+// epilogue are fenced (sched_barrier), so that "end of the write phase" is
+// the point where the pass's last LDS write has been issued.
 // The clock is read by every wave (a scalar instruction) and stored by one
 // lane of the workgroup, after the pre-epilogue barrier: there the stores
 // are older than every load and store the epilogue's hand-counted waits
 // count, and an older entry in the queue changes none of them.  The
-// epilogue-end stamp of a tile is stored with the next tile's, or after the
+// epilogue's stamps of a tile are stored with the next tile's, or after the
 // loop.
 #ifdef CC_GEMM_STAMPS
-#define CC_GEMM_STAMP_N 6
+#define CC_GEMM_STAMP_N 14
 __device__ unsigned long long* cc_gemm_stamp_buf;
 #define CC_STAMP(i) (stamp[i] = wall_clock64())
 #define CC_STAMP_IF(cond, i) \
   do {                       \
     if (cond) CC_STAMP(i);   \
   } while (0)
+#define CC_STAMP_FENCED(i)                \
+  do {                                    \
+    __builtin_amdgcn_sched_barrier(0);    \
+    CC_STAMP(i);                          \
+    __builtin_amdgcn_sched_barrier(0);    \
+  } while (0)
 #else
 #define CC_STAMP(i) ((void)0)
 #define CC_STAMP_IF(cond, i) ((void)0)
+#define CC_STAMP_FENCED(i) ((void)0)
 #endif
 
 template <int ACT, bool HAS_BIAS, bool HAS_RES, bool EPI_STAGED, bool LN_IN,
@@ -638,7 +666,16 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
 
 // compute cluster q: the 16 MFMAs of M-fragments 2q, 2q+1, on the fragments
 // the memory cluster before it read (same MFMAs, same order per accumulator
-// as ever: C is bit-identical whatever the schedule around them)
+// as ever: C is bit-identical whatever the schedule around them).
+//
+// The B fragment is the instruction's FIRST operand, so each MFMA computes
+// the TRANSPOSED fragment: lane l, register r of acc[m][n]
+// is C row 16 m + (l & 15), column 16 n + 4 (l >> 4) + r, four adjacent
+// columns of one row, where the natural order gives a lane four rows of one
+// column.  Both operand fragments have the same lane layout (row l & 15,
+// k 8 (l >> 4) .. + 8), so the reads, the staging and the hazards above do
+// not know which is which, and every accumulator receives the same products
+// over the same k in the same order as with the operands the other way round.
 #define PHASE_MFMA2(q)                                                      \
   do {                                                                      \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                      \
@@ -646,7 +683,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
       _Pragma("unroll") for (int m = 0; m < 2; m++) {                       \
         _Pragma("unroll") for (int n = 0; n < NFR2; n++) {                  \
           acc[2 * (q) + m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(    \
-              afrag[m][g], bfragT[n][g], acc[2 * (q) + m][n], 0, 0, 0);     \
+              bfragT[n][g], afrag[m][g], acc[2 * (q) + m][n], 0, 0, 0);     \
         }                                                                   \
       }                                                                     \
     }                                                                       \
@@ -748,7 +785,9 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
     CC_STAMP(4);
     if (tid == 0 && cc_gemm_stamp_buf) {
       unsigned long long* s = cc_gemm_stamp_buf;
-      if (stamp_tile >= 0) s[stamp_tile * CC_GEMM_STAMP_N + 5] = stamp[5];
+      if (stamp_tile >= 0)
+        for (int i = 5; i < CC_GEMM_STAMP_N; i++)
+          s[stamp_tile * CC_GEMM_STAMP_N + i] = stamp[i];
       stamp_tile = (long)blockIdx.x + (long)rep * (long)gridDim.x;
       for (int i = 0; i < 5; i++) s[stamp_tile * CC_GEMM_STAMP_N + i] = stamp[i];
     }
@@ -832,40 +871,55 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
 
     // ---- epilogue ----
     // bf16 output (all tower-internal GEMMs): LDS-staged + coalesced.
-    // The fragment C/D map scatters 2-byte lanes (col = lane&15, row =
-    // 4*(lane>>4)+r): storing it directly costs one 2 B store per
-    // element and the same pattern for the fused residual loads — the
-    // dominant cost at the thin ViT shapes once the K-loop is fed
-    // (attn_out 429 vs ~790 TF bare, profiles/r02_persist_ab.log).
+    // The transposed fragment map (PHASE_MFMA2) gives a lane four adjacent
+    // columns of one row (row = lane&15, col = 4*(lane>>4)+r): stored
+    // directly that is one 8 B store per fragment, 16 rows apart, and the
+    // same pattern for the fused residual loads (the natural map, 2 B
+    // scatters, was the dominant cost at the thin ViT shapes once the
+    // K-loop was fed: attn_out 429 vs ~790 TF bare,
+    // profiles/r02_persist_ab.log).
     // Instead: 4 passes of 2 M-fragments stage bf16(act(acc+bias))
     // through this wave's free 4 KB slice of A-buf1 (last read before
     // the barrier above; the next prologue writes only A-buf0/B-bufs),
+    // one packed 8 B LDS write per fragment,
     // then read back row-contiguous 16 B chunks, fuse the residual add
     // in f32, and store full b128s (8 lanes cover 128 contiguous
     // bytes of a C row).  Residual numerics: the pre-residual value is
     // rounded to bf16 once before the f32 add — one extra rounding vs
     // the scalar path, inside the embedding-cosine contract.
-    const long crow_base = ebm + waveM * WM2 + 4 * (lane >> 4);
-    const long ccol_base = ebn + waveN * WN2 + (lane & 15);
+    const long crow_base = ebm + waveM * WM2 + (lane & 15);
+    const long ccol_base = ebn + waveN * WN2 + 4 * (lane >> 4);
     if (staged) {
       issue_res(0);
       issue_res(1);
       issue_res(2);
       next_prologue();
       __bf16* slice = A2T(1) + wid * 2048;  // 4 KB per wave
-      // bias and column sum depend only on the n-fragment: 4 values per
-      // lane each, read from this tile's column table (landed by the
-      // rep-top wait, published by the rep-top barrier)
-      float bhoist[NFR2] = {};
-      float shoist[NFR2] = {};  // LN_IN: column sums of the folded weight
-      if constexpr (COLTAB) {
-        const float* ct = COLTAB_AT(rep & 1) + waveN * WN2 + (lane & 15);
-#pragma unroll
-        for (int n = 0; n < NFR2; n++) {
-          bhoist[n] = ct[n * FRAG];
-          if constexpr (LN_IN) shoist[n] = ct[BN2 + n * FRAG];
-        }
-      }
+      // The slice is 32 rows x 64 bf16, a 128-byte row stride with no room
+      // for padding, so the 16-byte chunk c of row R lives at chunk
+      // c ^ ((R >> 1) & 7).  Banks: 64 of 4 bytes, so a row is 32 banks,
+      // even rows on banks 0-31 and odd rows on 32-63, and a 16-byte chunk
+      // is one of 16 "bank quads": quad = 8 (R & 1) + (c ^ ((R >> 1) & 7)).
+      // - write (8 bytes per lane, served 32 lanes at a time): lanes
+      //   0-31 (32-63) are rows 16 mm + 0..15 and the two halves of chunk
+      //   2 n (2 n + 1).  Over the 8 even rows (R >> 1) & 7 takes each of
+      //   0..7 once, so c ^ it does too, the same over the 8 odd rows: 16
+      //   rows on 16 distinct quads, the two 8-byte halves of a quad from
+      //   two lanes, 64 banks once.  Unswizzled, the 8 rows of a parity
+      //   share one quad: an 8-way conflict.  (Served 16 lanes at a time it
+      //   is half of the same picture.)
+      // - read-back (16 bytes per lane, served 16 lanes at a time): 16
+      //   lanes are two adjacent rows, an even and an odd one, times all 8
+      //   chunks; the XOR permutes the chunks within a row, so each row
+      //   still covers its 32 banks once.
+      // For a write lane R = 16 mm + (lane & 15) and c = 2 n + (lane >> 5),
+      // so the XOR term does not depend on mm or n: wsw below.  For a
+      // read-back lane R = 8 i + (lane >> 3) and c = lane & 7, so
+      // (R >> 1) & 7 = 4 (i & 1) + (lane >> 4).
+      const int wsw = ((lane >> 1) & 7) ^ (lane >> 5);
+      const int wbase = (lane & 15) * 64 + 4 * ((lane >> 4) & 1);
+      const int rbase = (lane >> 3) * 64;
+      const int rchunk = (lane & 7) ^ (lane >> 4);
       // Stores: one descriptor per tile for C (and one for the stats),
       // base = the tile's first row, num_records = the bytes of the rows
       // of this tile that exist.  A lane's byte offset is (tile row, column),
@@ -891,35 +945,51 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
 #pragma unroll
       for (int p = 0; p < 4; p++) {
 #pragma unroll
-        for (int mm = 0; mm < 2; mm++) {
-          const int m = 2 * p + mm;
-          float2 mr[4] = {};  // LN_IN: (mean, rstd) of this lane's 4 rows
-          if constexpr (LN_IN) {
-            // read as float, not float2: hipcc puts a vmcnt(0) in front
-            // of an LDS read that its type-based alias analysis cannot
-            // tell from the LDS-DMA in flight (the prologue's), and it can
-            // tell a float from the DMA's dwords but not a HIP vector type
-            const float* t = LNTAB(rep & 1) +
-                             2 * (waveM * WM2 + m * FRAG + 4 * (lane >> 4));
+        for (int n = 0; n < NFR2; n++) {
+          // bias and column sum of this lane's four columns, read from this
+          // tile's column table (landed by the rep-top wait, published by
+          // the rep-top barrier) where they are used: all 16 + 16 of a lane
+          // held across the passes would not fit the register budget.
+          // Read as float, not as a vector: hipcc puts a vmcnt(0) in front
+          // of an LDS read that its type-based alias analysis cannot tell
+          // from the LDS-DMA in flight (the prologue's), and it can tell a
+          // float from the DMA's dwords but not a HIP vector type
+          float b4[4] = {};
+          float s4[4] = {};  // LN_IN: column sums of the folded weight
+          if constexpr (COLTAB) {
+            const float* ct = COLTAB_AT(rep & 1) + waveN * WN2 + n * FRAG +
+                              4 * (lane >> 4);
 #pragma unroll
-            for (int r = 0; r < 4; r++)
-              mr[r] = make_float2(t[2 * r], t[2 * r + 1]);
+            for (int r = 0; r < 4; r++) {
+              b4[r] = ct[r];
+              if constexpr (LN_IN) s4[r] = ct[BN2 + r];
+            }
           }
 #pragma unroll
-          for (int n = 0; n < NFR2; n++) {
-            const float bval = bhoist[n];
-            const int lrow_b = mm * 16 + 4 * (lane >> 4);
-            const int lcol = n * FRAG + (lane & 15);
+          for (int mm = 0; mm < 2; mm++) {
+            const int m = 2 * p + mm;
+            float mean = 0.0f, rstd = 0.0f;  // LN_IN: of this lane's one row
+            if constexpr (LN_IN) {
+              const float* t =
+                  LNTAB(rep & 1) + 2 * (waveM * WM2 + m * FRAG + (lane & 15));
+              mean = t[0];
+              rstd = t[1];
+            }
+            float v[4];
 #pragma unroll
             for (int r = 0; r < 4; r++) {
               if constexpr (LN_IN)
-                acc[m][n][r] = mr[r].y * (acc[m][n][r] - mr[r].x * shoist[n]);
-              float v = cc_act<ACT>(acc[m][n][r] + bval);
-              *(unsigned short*)(slice + (lrow_b + r) * 64 + lcol) =
-                  f32_to_bf16_rne(v);
+                acc[m][n][r] = rstd * (acc[m][n][r] - mean * s4[r]);
+              v[r] = cc_act<ACT>(acc[m][n][r] + b4[r]);
             }
+            // a 64-bit integer, not a vector type, for the reason above
+            *(unsigned long long*)(slice + wbase + mm * 1024 +
+                                   (((2 * n) ^ wsw) << 3)) =
+                (unsigned long long)f32x2_to_bf16x2(v[0], v[1]) |
+                ((unsigned long long)f32x2_to_bf16x2(v[2], v[3]) << 32);
           }
         }
+        CC_STAMP_FENCED(6 + p);
         if constexpr (HAS_RES) {
           if (p == 0) {
             issue_res(3);
@@ -940,7 +1010,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-          const int elem = i * 512 + lane * 8;
+          // row 8 i + lane / 8, chunk lane & 7 of the slice, unswizzled
+          const int elem = i * 512 + rbase + ((rchunk ^ (4 * (i & 1))) << 3);
           const int ro = row_off + (p * 32 + i * 8) * n32;  // tile row x N
           const bool col_ok = col_abs < n32;  // N % 8 == 0 always
           const unsigned c_off = col_ok ? (unsigned)(ro + col_abs) * 2 : OOB;
@@ -976,40 +1047,68 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
             __builtin_amdgcn_raw_buffer_store_b64(st, s_rsrc, (int)s_off, 0, 0);
           }
         }
+        CC_STAMP_FENCED(10 + p);
       }
 #undef RES_WAIT
     } else {
-      // scalar store path (f32 outputs always; bf16 when epi_staged=0).
-      // bias hoisted exactly like the staged path: 4 loads per lane
-      // instead of one dependent load per fragment (the old
-      // per-element-load serialization, guide trap (c)).
+      // direct store path (f32 outputs always; bf16 when epi_staged=0):
+      // a lane stores its four adjacent columns of a fragment at once, 8
+      // bytes of bf16 or 16 of f32, where the tile is interior and the
+      // rows of C keep the alignment (f32 outputs need not have
+      // N % 4 == 0); element by element, each one guarded, on the M and N
+      // edges and otherwise.  The bias is read from the column table where
+      // it is used, four values per fragment, as in the staged path.
       next_prologue();
       const bool interior = (ebm + BM2 <= M) && (ebn + BN2 <= N);
-      float bhoist2[NFR2] = {};
-      if constexpr (HAS_BIAS) {
-        // from the column table as well (a column >= N reads a clamped
-        // value that is never stored)
-        const float* ct = COLTAB_AT(rep & 1) + waveN * WN2 + (lane & 15);
+      const bool packed =
+          interior && (N & 3) == 0 && ((unsigned long long)C & 15) == 0 &&
+          (!HAS_RES || ((unsigned long long)residual & 7) == 0);
 #pragma unroll
-        for (int n = 0; n < NFR2; n++) bhoist2[n] = ct[n * FRAG];
-      }
+      for (int n = 0; n < NFR2; n++) {
+        const long col = ccol_base + n * FRAG;
+        float b4[4] = {};
+        if constexpr (HAS_BIAS) {
+          // a column >= N reads a clamped value that is never stored
+          const float* ct =
+              COLTAB_AT(rep & 1) + waveN * WN2 + n * FRAG + 4 * (lane >> 4);
 #pragma unroll
-      for (int m = 0; m < MFR2; m++) {
+          for (int r = 0; r < 4; r++) b4[r] = ct[r];
+        }
 #pragma unroll
-        for (int n = 0; n < NFR2; n++) {
-          const long col = ccol_base + n * FRAG;
-          if (!interior && col >= N) continue;
-          const float bval = bhoist2[n];
+        for (int m = 0; m < MFR2; m++) {
+          const long row = crow_base + m * FRAG;
+          float v[4];
 #pragma unroll
-          for (int r = 0; r < 4; r++) {
-            const long row = crow_base + m * FRAG + r;
-            if (!interior && row >= M) continue;
-            float v = cc_act<ACT>(acc[m][n][r] + bval);
-            if constexpr (HAS_RES) v += (float)residual[row * N + col];
-            if (c_is_bf16)
-              ((unsigned short*)C)[row * N + col] = f32_to_bf16_rne(v);
-            else
-              ((float*)C)[row * N + col] = v;
+          for (int r = 0; r < 4; r++) v[r] = cc_act<ACT>(acc[m][n][r] + b4[r]);
+          if (packed) {
+            if constexpr (HAS_RES) {
+              const u32x2 r2 = *(const u32x2*)(residual + row * N + col);
+#pragma unroll
+              for (int r = 0; r < 4; r++)
+                v[r] += __builtin_bit_cast(
+                    float, (r2[r >> 1] >> (16 * (r & 1))) << 16);
+            }
+            if (c_is_bf16) {
+              u32x2 o;
+              o[0] = f32x2_to_bf16x2(v[0], v[1]);
+              o[1] = f32x2_to_bf16x2(v[2], v[3]);
+              *(u32x2*)((__bf16*)C + row * N + col) = o;
+            } else {
+              f32x4 o = {v[0], v[1], v[2], v[3]};
+              *(f32x4*)((float*)C + row * N + col) = o;
+            }
+          } else {
+            if (row >= M) continue;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+              if (col + r >= N) continue;
+              float w = v[r];
+              if constexpr (HAS_RES) w += (float)residual[row * N + col + r];
+              if (c_is_bf16)
+                ((__bf16*)C)[row * N + col + r] = (__bf16)w;
+              else
+                ((float*)C)[row * N + col + r] = w;
+            }
           }
         }
       }
@@ -1019,7 +1118,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_t256(
   }
 #ifdef CC_GEMM_STAMPS
   if (tid == 0 && stamp_tile >= 0)
-    cc_gemm_stamp_buf[stamp_tile * CC_GEMM_STAMP_N + 5] = stamp[5];
+    for (int i = 5; i < CC_GEMM_STAMP_N; i++)
+      cc_gemm_stamp_buf[stamp_tile * CC_GEMM_STAMP_N + i] = stamp[i];
 #endif
 #undef LNTAB
 #undef STAGE_LN2

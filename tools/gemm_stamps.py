@@ -15,7 +15,14 @@ production library never carries the stamps.
 Stamps per tile (100 MHz wall clock, read by every wave, stored by one
 lane): 0 rep top, 1-3 the barriers in front of the first three MFMA clusters
 of the tile's first K-tile, 4 the end of the K-loop, 5 the end of the
-epilogue.  A workgroup's next rep top follows its epilogue end directly, so
+epilogue, 6 + p the end of the write phase of the staged epilogue's pass p
+(accumulators -> bf16 -> the wave's LDS slice), 10 + p the end of its
+read-back (LDS -> residual add, statistics -> store issue).  "write p0" is
+(6 - 4): it also holds the issue of the first residual loads and of the next
+tile's prologue; "write p1-3" is the sum of (6 + p) - (10 + p - 1) over the
+other three passes, the write phase alone; "read-back" is the sum of
+(10 + p) - (6 + p) over the four, which includes the wait for the pass's
+residual loads.  A workgroup's next rep top follows its epilogue end directly, so
 (5 - 4) is everything between two K-loops except the rep-top wait, which
 is (next 0 - 5).  "kernel us" is the last stamp 5 minus the first stamp 0 of
 a launch: set it against the production library's kernel time to see what
@@ -39,7 +46,7 @@ if str(ROOT) not in sys.path:
 from cosmos_curate_amd import build as cc_build  # noqa: E402
 
 LIB = ROOT / "tools" / "libcchot_stamps.so"
-STAMP_N = 6
+STAMP_N = 14
 M_FLAGSHIP = 224 * 21 * 50  # clips x frames x tokens
 
 # (name, N, K, form of tools/gemm_epilogue_golden.py)
@@ -124,12 +131,16 @@ def run(lib_path: pathlib.Path, M: int, launches: int) -> None:
           f"launches after 2 of warm-up")
     print(f"{'gemm':9s} {'N':>5s} {'K':>5s} {'tiles':>6s} {'KT':>3s} | "
           f"{'kernel us':>9s} {'K-loop us':>9s} {'us/K-tile':>9s} {'phase 0':>8s} "
-          f"{'phase 1':>8s} {'epilogue us':>11s} {'rep-top us':>10s} "
+          f"{'phase 1':>8s} {'epilogue us':>11s} {'write p0':>8s} "
+          f"{'write p1-3':>10s} {'read-back':>9s} {'rep-top us':>10s} "
           f"{'tile round us':>13s}")
     for name, N, K, grid, runs in collect(lib_path, M, launches):
-        acc = torch.zeros(7, dtype=torch.float64)
+        acc = torch.zeros(10, dtype=torch.float64)
         for s in runs:
             assert (s[:, 5] >= s[:, 4]).all() and (s[:, 4] > s[:, 0]).all()
+            assert (s[:, 6] >= s[:, 4]).all() and (s[:, 5] >= s[:, 13]).all()
+            wr = sum(s[:, 6 + p] - s[:, 9 + p] for p in (1, 2, 3))
+            rb = sum(s[:, 10 + p] - s[:, 6 + p] for p in range(4))
             nxt = s[grid:, 0] - s[:-grid, 5]
             rnd = s[grid:, 0] - s[:-grid, 0]
             nan = torch.tensor(float("nan"), dtype=torch.float64)
@@ -137,13 +148,14 @@ def run(lib_path: pathlib.Path, M: int, launches: int) -> None:
                 s[:, 5].max() - s[:, 0].min(),
                 (s[:, 4] - s[:, 0]).mean(), (s[:, 2] - s[:, 1]).mean(),
                 (s[:, 3] - s[:, 2]).mean(), (s[:, 5] - s[:, 4]).mean(),
+                (s[:, 6] - s[:, 4]).mean(), wr.mean(), rb.mean(),
                 nxt.mean() if len(nxt) else nan,
                 rnd.mean() if len(rnd) else nan])
-        ker, kl, p0, p1, epi, top, rnd = (acc / len(runs)).tolist()
+        ker, kl, p0, p1, epi, w0, wr, rb, top, rnd = (acc / len(runs)).tolist()
         kt = K // 64
         print(f"{name:9s} {N:5d} {K:5d} {len(runs[0]):6d} {kt:3d} | {ker:9.1f} "
               f"{kl:9.2f} {kl / kt:9.3f} {p0:8.3f} {p1:8.3f} {epi:11.2f} "
-              f"{top:10.2f} {rnd:13.2f}")
+              f"{w0:8.2f} {wr:10.2f} {rb:9.2f} {top:10.2f} {rnd:13.2f}")
 
 
 def main():
