@@ -22,6 +22,9 @@ Per-file flags:
   cc_attnpool.hip; the arithmetic is the f32 MFMA and ordered f64 adds, so
   contraction has nothing to contract.
 - cc_dedupseg.hip: cc_kmeans.hip's flags, for the same f32 MFMA and compares.
+- cc_motionscore.hip: -ffp-contract=off — the magnitude and the bilinear blend
+  are the f32 chains of the torch path and of oracle/motion.py, product by
+  product; an FMA would round them differently.
 """
 
 from __future__ import annotations
@@ -55,6 +58,7 @@ SOURCES: list[tuple[str, list[str]]] = [
     ("cc_attnpool.hip", [ARCH, *NO_PK_F32]),
     ("cc_kmeans.hip", [ARCH, *NO_PK_F32]),
     ("cc_dedupseg.hip", [ARCH, *NO_PK_F32]),
+    ("cc_motionscore.hip", [ARCH, "-ffp-contract=off"]),
 ]
 
 

@@ -104,6 +104,37 @@ class PairwiseSegPlan(ctypes.Structure):
     ]
 
 
+class MotionScorePlan(ctypes.Structure):
+    """cc_motion_score_plan_info: how a motion-score call would be launched
+    (the est_* fields are cc_motion_score_blocks', the rest
+    cc_motion_score_rows')."""
+
+    _fields_ = [
+        ("tile_w", ctypes.c_int32),
+        ("tile_h", ctypes.c_int32),
+        ("tiles_x", ctypes.c_int32),
+        ("tiles_y", ctypes.c_int32),
+        ("tiles_per_frame", ctypes.c_int32),
+        ("taps_per_frame", ctypes.c_int32),
+        ("block", ctypes.c_int32),
+        ("zero_grid", ctypes.c_int32),
+        ("bin_grid", ctypes.c_int32),
+        ("scan_grid", ctypes.c_int32),
+        ("scan_block", ctypes.c_int32),
+        ("paint_grid", ctypes.c_int32),
+        ("finish_grid", ctypes.c_int32),
+        ("est_partials", ctypes.c_int32),
+        ("est_grid", ctypes.c_int32),
+        ("partial_bytes", ctypes.c_int64),
+        ("tap_bytes", ctypes.c_int64),
+        ("count_bytes", ctypes.c_int64),
+        ("start_bytes", ctypes.c_int64),
+        ("workspace_bytes", ctypes.c_int64),
+        ("est_partial_bytes", ctypes.c_int64),
+        ("est_workspace_bytes", ctypes.c_int64),
+    ]
+
+
 def _declare(lib: ctypes.CDLL) -> None:
     c = ctypes
     lib.cc_last_error.restype = c.c_char_p
@@ -264,6 +295,16 @@ def _declare(lib: ctypes.CDLL) -> None:
         c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64,
         c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64,
         c.c_uint64]
+    lib.cc_motion_score_plan.argtypes = [
+        c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int64,
+        c.c_int64, c.POINTER(MotionScorePlan)]
+    lib.cc_motion_score_rows.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64,
+        c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p,
+        c.c_int64, c.c_uint64]
+    lib.cc_motion_score_blocks.argtypes = [
+        c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_int64,
+        c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64, c.c_uint64]
     lib.cc_conv3x3_bf16.argtypes = [
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int,
         c.c_int, c.c_int, c.c_uint64]
@@ -788,6 +829,54 @@ def pairwise_seg_plan(m: int, d: int, k: int) -> PairwiseSegPlan:
     plan = PairwiseSegPlan()
     check(load().cc_pairwise_seg_plan(m, d, k, ctypes.byref(plan)))
     return plan
+
+
+def motion_score_plan(n_frames: int, n_rows: int, n_clips: int, h: int, w: int,
+                      oh: int, ow: int) -> MotionScorePlan:
+    """The launch plan of a motion-score call over ``n_frames`` h x w frames
+    holding ``n_rows`` MV rows, cut into ``n_clips`` clips and scored on an
+    (oh, ow) patch grid (cc_motion_score_plan; host-only).  Raises on what
+    cc_motion_score_rows / cc_motion_score_blocks themselves would reject."""
+    plan = MotionScorePlan()
+    check(load().cc_motion_score_plan(n_frames, n_rows, n_clips, h, w, oh, ow,
+                                      ctypes.byref(plan)))
+    return plan
+
+
+def motion_patch_grid(h: int, w: int) -> tuple[int, int]:
+    """(oh, ow) of the per-patch-256 score: Python's half-even round, which
+    the library takes as given and never recomputes."""
+    return max(1, round(h / 256)), max(1, round(w / 256))
+
+
+def motion_score_rows(
+    rows_ptr: int, frame_offsets_ptr: int, clip_offsets_ptr: int, n_rows: int,
+    n_frames: int, n_clips: int, h: int, w: int, oh: int, ow: int,
+    out_ptr: int, workspace_ptr: int, workspace_bytes: int, stream: int,
+) -> None:
+    """(per_patch_min, global_mean) as f64 pairs into ``out_ptr`` [n_clips, 2]
+    from (n, 10) f32 MV rows on device pointers (cc_motion_score_rows):
+    int64 ``frame_offsets`` [n_frames + 1] index rows, int32 ``clip_offsets``
+    [n_clips + 1] index frames.  The workspace holds at least
+    ``motion_score_plan(...).workspace_bytes``.  No fallback: a failing call
+    raises."""
+    check(load().cc_motion_score_rows(
+        rows_ptr or None, frame_offsets_ptr, clip_offsets_ptr, n_rows, n_frames,
+        n_clips, h, w, oh, ow, out_ptr, workspace_ptr, workspace_bytes, stream))
+
+
+def motion_score_blocks(
+    field_ptr: int, clip_offsets_ptr: int, n_frames: int, n_clips: int, h: int,
+    w: int, oh: int, ow: int, out_ptr: int, workspace_ptr: int,
+    workspace_bytes: int, stream: int,
+) -> None:
+    """The same scores from the int16 [n_frames, ceil(h/16), ceil(w/16), 2]
+    block field estimate_motion writes (cc_motion_score_blocks); the workspace
+    holds at least ``motion_score_plan(n_frames, 0, ...).est_workspace_bytes``.
+    No fallback: a failing call raises."""
+    check(load().cc_motion_score_blocks(
+        field_ptr or None, clip_offsets_ptr, n_frames, n_clips, h, w, oh, ow,
+        out_ptr, workspace_ptr, workspace_bytes, stream))
 
 
 class VideoInfo(ctypes.Structure):

@@ -91,23 +91,22 @@ def motion_sample_pairs(
     return [(i - 1, i) for i in range(step, n_frames, step)][:max_frames]
 
 
-def estimate_clip_motion(
+def _estimate_on_device(
     data: bytes | npt.NDArray[np.uint8], *,
     target_fps: float = 2.0, target_duration_ratio: float = 0.5,
     search_range: int = 16, mv_lambda: int = 4,
-) -> DecodedMotionData:
-    """Raw payload (version 1 or 2) -> per-sampled-frame MV arrays.
-
-    One host gather of the luma planes the pairs need, one upload, one
-    kernel launch for all pairs on the current stream, one copy back.
-    """
+) -> tuple[torch.Tensor | None, int, int]:
+    """Raw payload -> (int16 [n, nby, nbx, 2] block field on the device, or
+    None when no pair is sampled; h; w).  One host gather of the luma planes
+    the pairs need, one upload, one kernel launch for all pairs on the
+    current stream; nothing is copied back."""
     n_frames, h, w, fps = raw_backend.parse_header(data)
     if h < MIN_SIDE or w < MIN_SIDE:
         msg = f"video resolution {w}x{h} is below {MIN_SIDE} on a side"
         raise VideoResolutionTooSmallError(msg)
     pairs = motion_sample_pairs(n_frames, fps, target_fps, target_duration_ratio)
     if not pairs:
-        return DecodedMotionData(frames=[], frame_size=(h, w))
+        return None, h, w
     depth, _, _, bps = raw_backend.parse_format(data)
 
     hotpath.require_gpu()
@@ -134,10 +133,57 @@ def estimate_clip_motion(
         mv.data_ptr(), stream, frame_stride_bytes=stride_frames * plane,
         bit_depth=depth, search_range=search_range, mv_lambda=mv_lambda,
     )
+    return mv, h, w
+
+
+def estimate_clip_motion(
+    data: bytes | npt.NDArray[np.uint8], *,
+    target_fps: float = 2.0, target_duration_ratio: float = 0.5,
+    search_range: int = 16, mv_lambda: int = 4,
+) -> DecodedMotionData:
+    """Raw payload (version 1 or 2) -> per-sampled-frame MV arrays: the
+    device field of ``_estimate_on_device``, one copy back, expanded to rows
+    on the host."""
+    mv, h, w = _estimate_on_device(
+        data, target_fps=target_fps, target_duration_ratio=target_duration_ratio,
+        search_range=search_range, mv_lambda=mv_lambda)
+    if mv is None:
+        return DecodedMotionData(frames=[], frame_size=(h, w))
     mv_host = mv.cpu().numpy()  # synchronises the stream
     return DecodedMotionData(
         frames=[blocks_to_mv_rows(m, h, w) for m in mv_host], frame_size=(h, w)
     )
+
+
+def score_blocks_native(mv: torch.Tensor, h: int, w: int) -> tuple[float, float]:
+    """(per_patch_min, global_mean) of one clip from its int16 block field on
+    the device (cc_motion_score_blocks) on the current stream: what
+    ``score_clips_native`` gives for ``blocks_to_mv_rows`` of the field.  Only
+    the two scalars come back."""
+    n = mv.shape[0]
+    oh, ow = hotpath.motion_patch_grid(h, w)
+    plan = hotpath.motion_score_plan(n, 0, 1, h, w, oh, ow)
+    stream = torch.cuda.current_stream(mv.device).cuda_stream
+    clip_off = torch.tensor([0, n], dtype=torch.int32).to(mv.device, non_blocking=True)
+    ws = torch.empty(plan.est_workspace_bytes, dtype=torch.uint8, device=mv.device)
+    out = torch.empty((1, 2), dtype=torch.float64, device=mv.device)
+    hotpath.motion_score_blocks(
+        mv.data_ptr(), clip_off.data_ptr(), n, 1, h, w, oh, ow, out.data_ptr(),
+        ws.data_ptr(), plan.est_workspace_bytes, stream)
+    per_patch_min, global_mean = out.cpu().tolist()[0]
+    return per_patch_min, global_mean
+
+
+def score_clip_motion(
+    data: bytes | npt.NDArray[np.uint8], **estimate_kwargs,
+) -> tuple[float, float]:
+    """Raw payload -> (per_patch_min, global_mean): cc_motion_estimate straight
+    into cc_motion_score_blocks on one stream.  The vectors never leave the
+    device.  A payload that samples no pair scores (0, 0)."""
+    mv, h, w = _estimate_on_device(data, **estimate_kwargs)
+    if mv is None:
+        return 0.0, 0.0
+    return score_blocks_native(mv, h, w)
 
 
 class MotionVectorEstimationStage(CuratorStage):

@@ -7,12 +7,16 @@ Mirror of /root/reference/cosmos_curate/pipelines/video/filtering/motion/
 small-motion clips to ``filtered_clips``.
 
 MI355X status of the two halves:
-- the SCORE math runs here on torch (GPU when available) mirroring the
+- the SCORE has two backends.  "torch" (the default) mirrors the
   reference's tensor pipeline; its scatter paint
   (torch.index_put_(accumulate=False)) has UNDEFINED duplicate-index order
-  upstream, so parity with oracle/motion.py is pinned at score level.  The
-  paint is bandwidth-trivial (<< 1 % of a clip's budget) — no dedicated
-  HIP kernel until the semantics are worth pinning tighter.
+  upstream, so parity with oracle/motion.py is pinned at score level.
+  "native" is cc_motion_score_rows (csrc/cc_motionscore.hip, DESIGN.md
+  §28): the same two scores without the flow field, every clip of a frame
+  size in one call, with the overlap order pinned — the row with the
+  highest (position of its block size in BLOCK_OPTIONS, row index) owns a
+  pixel, which is what the torch path yields when index_put_ writes
+  sequentially.
 - MV EXTRACTION needs decoder side-data (decode_for_motion,
   motion_vector_backend.py:169-250 — the export_mvs decoder flag): that is
   the same rocDecode seam as frame decode.  Clips carry
@@ -28,6 +32,7 @@ import numpy as np
 import numpy.typing as npt
 import torch
 
+from cosmos_curate_amd import hotpath
 from cosmos_curate_amd.core.interfaces.stage_interface import (
     CuratorStage,
     CuratorStageResource,
@@ -85,6 +90,49 @@ def motion_vectors_to_flowfield(
     return flow
 
 
+def score_clips_native(clips: list[DecodedMotionData]) -> list[tuple[float, float]]:
+    """(per_patch_min, global_mean) of every clip through
+    cc_motion_score_rows.  Clips are grouped by frame size; a group is one
+    upload (rows, frame offsets and clip offsets in one pinned buffer), one
+    call and one read-back.  Requires the GPU; no fallback."""
+    hotpath.require_gpu()
+    scores: list[tuple[float, float]] = [(0.0, 0.0)] * len(clips)
+    groups: dict[tuple[int, int], list[int]] = {}
+    for i, clip in enumerate(clips):
+        groups.setdefault(tuple(clip.frame_size), []).append(i)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    for (h, w), members in groups.items():
+        frames = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, 10)
+                  for i in members for f in clips[i].frames]
+        frame_off = np.zeros(len(frames) + 1, dtype=np.int64)
+        np.cumsum([len(f) for f in frames], out=frame_off[1:])
+        clip_off = np.zeros(len(members) + 1, dtype=np.int32)
+        np.cumsum([len(clips[i].frames) for i in members], out=clip_off[1:])
+        n_rows, n_frames, n_clips = int(frame_off[-1]), len(frames), len(members)
+        oh, ow = hotpath.motion_patch_grid(h, w)
+        plan = hotpath.motion_score_plan(n_frames, n_rows, n_clips, h, w, oh, ow)
+        # rows (40 B each, so the int64 offsets behind them stay aligned),
+        # frame offsets, clip offsets
+        b_rows, b_foff = 40 * n_rows, 40 * n_rows + frame_off.nbytes
+        host = torch.empty(b_foff + clip_off.nbytes, dtype=torch.uint8).pin_memory()
+        packed = host.numpy()
+        if n_rows:
+            packed[:b_rows] = np.concatenate(frames).view(np.uint8).reshape(-1)
+        packed[b_rows:b_foff] = frame_off.view(np.uint8)
+        packed[b_foff:] = clip_off.view(np.uint8)
+        buf = host.to(dev, non_blocking=True)
+        ws = torch.empty(plan.workspace_bytes, dtype=torch.uint8, device=dev)
+        out = torch.empty((n_clips, 2), dtype=torch.float64, device=dev)
+        hotpath.motion_score_rows(
+            buf.data_ptr(), buf.data_ptr() + b_rows, buf.data_ptr() + b_foff,
+            n_rows, n_frames, n_clips, h, w, oh, ow, out.data_ptr(),
+            ws.data_ptr(), plan.workspace_bytes, stream)
+        for i, (patch_min, gmean) in zip(members, out.cpu().tolist()):
+            scores[i] = (patch_min, gmean)
+    return scores
+
+
 def check_if_small_motion(
     mv_list: list[npt.NDArray[np.float32]],
     frame_shape: tuple[int, int],
@@ -93,8 +141,19 @@ def check_if_small_motion(
     *,
     use_gpu: bool = False,
     batch_size: int = 256,
+    backend: str = "torch",
 ) -> tuple[bool, float, float]:
-    """motion_vector_backend.py:253-313 semantics."""
+    """motion_vector_backend.py:253-313 semantics.  ``backend="native"``
+    scores through cc_motion_score_rows (GPU required) and compares against
+    the thresholds on the host in f64."""
+    if backend == "native":
+        per_patch_min, global_mean = score_clips_native(
+            [DecodedMotionData(list(mv_list), tuple(frame_shape))])[0]
+        small = (global_mean < global_mean_threshold
+                 or per_patch_min < per_patch_min_256_threshold)
+        return small, per_patch_min, global_mean
+    if backend != "torch":
+        raise ValueError(f"backend must be 'torch' or 'native', got {backend!r}")
     h, w = frame_shape
     device = torch.device("cuda" if use_gpu else "cpu")
     global_sum = torch.tensor(0.0, device=device, dtype=torch.float64)
@@ -137,7 +196,12 @@ class MotionFilterStage(CuratorStage):
         num_gpus_per_worker: float = 0.25,
         verbose: bool = False,
         log_stats: bool = False,
+        score_backend: str = "torch",
     ) -> None:
+        if score_backend not in ("torch", "native"):
+            raise ValueError(
+                f"score_backend must be 'torch' or 'native', got {score_backend!r}")
+        self._score_backend = score_backend
         self._timer = StageTimer(self)
         self._global_mean_threshold = global_mean_threshold
         self._per_patch_threshold = per_patch_min_256_threshold
@@ -157,18 +221,32 @@ class MotionFilterStage(CuratorStage):
             with self._timer.time_process():
                 for video in task.videos:
                     kept = []
+                    native: dict[int, tuple[float, float]] = {}
+                    if self._score_backend == "native":
+                        # every clip of the video in one batch a frame size
+                        scored = [c for c in video.clips
+                                  if c.decoded_motion_data is not None
+                                  and c.decoded_motion_data.frames]
+                        if scored:
+                            native = dict(zip(map(id, scored), score_clips_native(
+                                [c.decoded_motion_data for c in scored])))
                     for clip in video.clips:
                         md = clip.decoded_motion_data
                         if md is None or not md.frames:
                             clip.errors["motion"] = "motion_decode_unavailable"
                             kept.append(clip)
                             continue
-                        small, patch_min, gmean = check_if_small_motion(
-                            md.frames, md.frame_size,
-                            self._global_mean_threshold,
-                            self._per_patch_threshold,
-                            use_gpu=use_gpu,
-                        )
+                        if self._score_backend == "native":
+                            patch_min, gmean = native[id(clip)]
+                            small = (gmean < self._global_mean_threshold
+                                     or patch_min < self._per_patch_threshold)
+                        else:
+                            small, patch_min, gmean = check_if_small_motion(
+                                md.frames, md.frame_size,
+                                self._global_mean_threshold,
+                                self._per_patch_threshold,
+                                use_gpu=use_gpu,
+                            )
                         clip.motion_score_global_mean = gmean
                         clip.motion_score_per_patch_min_256 = patch_min
                         clip.decoded_motion_data = None  # free MV payload

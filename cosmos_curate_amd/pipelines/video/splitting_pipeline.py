@@ -219,6 +219,7 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
             global_mean_threshold=args.motion_global_mean_threshold,
             per_patch_min_256_threshold=args.motion_per_patch_min_256_threshold,
             score_only=args.motion_filter == "score-only",
+            score_backend=args.motion_score_backend,
             log_stats=True,
         ))
     iv2 = args.embedding_algorithm == "internvideo2"
@@ -342,6 +343,12 @@ def _setup_parser(parser: argparse.ArgumentParser) -> None:
                         help="where the motion filter's vectors come from: "
                         "none (clips must already carry them) or estimate "
                         "(GPU block matching on the luma of raw payloads)")
+    parser.add_argument("--motion-score-backend", choices=["torch", "native"],
+                        default="torch",
+                        help="how the motion filter scores clips: the torch "
+                        "flow-field paint, or cc_motion_score_rows (hand-"
+                        "written HIP, every clip of a video in one call; "
+                        "needs a GPU)")
     parser.add_argument("--motion-decode-target-fps", type=float, default=2.0)
     parser.add_argument("--motion-decode-target-duration-ratio", type=float,
                         default=0.5)

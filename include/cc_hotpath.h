@@ -787,6 +787,74 @@ int cc_pairwise_max_earlier_seg(const void* e_f32, int64_t m, int64_t d,
                                 void* maxv_f32, void* argi_i32, void* workspace,
                                 int64_t workspace_bytes, uint64_t stream);
 
+/* ---- the motion filter's score without a flow field ------
+ * Replaces the scatter paint, norm, reductions and interpolate of
+ * check_if_small_motion (motion_vector_backend.py:85-313).  rows [n_rows][10]
+ * f32 = [w, h, src_x, src_y, dst_x, dst_y, flags, motion_x, motion_y,
+ * motion_scale]; frame_offsets int64 [n_frames + 1] cuts rows into frames,
+ * clip_offsets int32 [n_clips + 1] cuts frames into clips; all frames are
+ * h x w.  A row paints only if (w, h) is exactly (8,8), (16,16), (16,8) or
+ * (8,16) — its pass 0..3 — with delta = -motion / (scale == 0 ? 1 : scale) on
+ * the pixels trunc(clamp(dst_x + ox, 0, W-1)), ox in [-w/2, w/2) (f32 add,
+ * clamp, then truncation), likewise in y.  A pixel several rows cover belongs
+ * to the row with the highest (pass, row index in its frame): the order a
+ * sequential index_put_ per block size yields, NOT oracle/motion.py's pure row
+ * order; the two agree where only same-size blocks overlap.  An unpainted
+ * pixel has magnitude 0; mag = |delta| / (H + W) in f32.
+ * out f64 [n_clips][2], per clip of n frames:
+ *   [0] per_patch_min: the minimum of the (oh, ow) pixel-centre bilinear
+ *       downscale (f32 weights, oracle/motion.py::_bilinear_resize_f32) of the
+ *       f32-rounded temporal mean of mag
+ *   [1] global_mean = sum of mag / (max(n, 1) * H * W)
+ * A clip without frames scores (0, 0).  oh and ow come from the caller
+ * (Python's half-even round) and are not recomputed.  Sums are f64 in a fixed
+ * order and there are no floating-point atomics: the output depends on the
+ * arguments alone, bit for bit.  Offsets are never read back; rows outside
+ * their frame's range or past n_rows are ignored.
+ * cc_motion_score_blocks takes the int16 [n_frames][ceil(h/16)][ceil(w/16)][2]
+ * field cc_motion_estimate writes instead of rows and scores what
+ * blocks_to_mv_rows of it would score.
+ * CC_ERR_INVALID on null or misaligned pointers (rows, clip_offsets 4 bytes;
+ * frame_offsets, out 8; workspace 16; field 4), negative n_frames or n_rows,
+ * n_clips, h or w < 1, oh or ow outside [1, h] / [1, w], or a workspace below
+ * the plan's; CC_ERR_UNSUPPORTED on h or w above 16384, 2^28 rows or more
+ * (the owner key holds 28 bits of row index) or a grid above 2^31-1 — all
+ * before any launch.  Timed as "motion_score_bin" (zero, count, scan, fill),
+ * "motion_score_paint", "motion_score_blocks" and "motion_score_finish". */
+typedef struct cc_motion_score_plan_info {
+  int32_t tile_w, tile_h;    /* pixels one paint workgroup owns */
+  int32_t tiles_x, tiles_y;
+  int32_t tiles_per_frame;
+  int32_t taps_per_frame;    /* 2 oh * 2 ow */
+  int32_t block;             /* every kernel but the scan */
+  int32_t zero_grid;         /* ceil(frames * tiles / block) */
+  int32_t bin_grid;          /* count and fill: ceil(n_rows / block) */
+  int32_t scan_grid;         /* one workgroup a frame */
+  int32_t scan_block;
+  int32_t paint_grid;        /* frames * tiles */
+  int32_t finish_grid;       /* one workgroup a clip */
+  int32_t est_partials;      /* blocks path: partial sums a frame */
+  int32_t est_grid;          /* frames * est_partials */
+  int64_t partial_bytes, tap_bytes, count_bytes, start_bytes;
+  int64_t workspace_bytes;   /* rows path: the four above + 16 B a row */
+  int64_t est_partial_bytes;
+  int64_t est_workspace_bytes; /* blocks path: partials + taps */
+} cc_motion_score_plan_info;
+int cc_motion_score_plan(int64_t n_frames, int64_t n_rows, int64_t n_clips,
+                         int64_t h, int64_t w, int64_t oh, int64_t ow,
+                         cc_motion_score_plan_info* out);
+int cc_motion_score_rows(const void* rows_f32, const void* frame_offsets_i64,
+                         const void* clip_offsets_i32, int64_t n_rows,
+                         int64_t n_frames, int64_t n_clips, int64_t h,
+                         int64_t w, int64_t oh, int64_t ow, void* out_f64,
+                         void* workspace, int64_t workspace_bytes,
+                         uint64_t stream);
+int cc_motion_score_blocks(const void* field_i16, const void* clip_offsets_i32,
+                           int64_t n_frames, int64_t n_clips, int64_t h,
+                           int64_t w, int64_t oh, int64_t ow, void* out_f64,
+                           void* workspace, int64_t workspace_bytes,
+                           uint64_t stream);
+
 /* ---- kernel timing (bench.py roofline evidence) ---------------------
  * When enabled, every cc_* kernel launch is bracketed with hipEvents on
  * its launch stream; totals are accumulated per kernel name. */
