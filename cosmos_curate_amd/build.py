@@ -18,6 +18,7 @@ Per-file flags:
   numpy restatement, and the f32 chains say fmaf where they mean it.
 - cc_attnpool.hip: default contraction (MFMA; f32 softmax within a stated
   bound), packed-f32 instructions off.
+- cc_attncross.hip: cc_attnpool.hip's flags, for the same reasons.
 - cc_kmeans.hip: cc_dedup.hip's flags plus packed-f32 instructions off, as for
   cc_attnpool.hip; the arithmetic is the f32 MFMA and ordered f64 adds, so
   contraction has nothing to contract.
@@ -56,6 +57,7 @@ SOURCES: list[tuple[str, list[str]]] = [
     ("cc_conv.hip", [ARCH]),
     ("cc_tnheads.hip", [ARCH, "-ffp-contract=off"]),
     ("cc_attnpool.hip", [ARCH, *NO_PK_F32]),
+    ("cc_attncross.hip", [ARCH, *NO_PK_F32]),
     ("cc_kmeans.hip", [ARCH, *NO_PK_F32]),
     ("cc_dedupseg.hip", [ARCH, *NO_PK_F32]),
     ("cc_motionscore.hip", [ARCH, "-ffp-contract=off"]),

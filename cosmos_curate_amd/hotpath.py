@@ -67,6 +67,12 @@ class AttnPoolPlan(ctypes.Structure):
 ATTN_POOL_HEADS = 16  # rows of U: cc_attn_pool's MFMA dimension
 
 
+class AttnCrossPlan(ctypes.Structure):
+    """cc_attn_cross_plan_info: how a cc_attn_cross call would be launched."""
+
+    _fields_ = AttnPoolPlan._fields_
+
+
 class KmeansPlan(ctypes.Structure):
     """cc_kmeans_plan_info: how a k-means step would be launched."""
 
@@ -249,6 +255,14 @@ def _declare(lib: ctypes.CDLL) -> None:
         c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64,
         c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int, c.c_int, c.c_int,
         c.c_void_p, c.c_int64, c.c_uint64]
+    lib.cc_attn_cross_plan.argtypes = [
+        c.c_int64, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int,
+        c.POINTER(AttnCrossPlan)]
+    lib.cc_attn_cross_supported.argtypes = [c.c_int, c.c_int]
+    lib.cc_attn_cross.argtypes = [
+        c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64,
+        c.c_int, c.c_int, c.c_int, c.c_int, c.c_float, c.c_int, c.c_void_p,
+        c.c_int64, c.c_uint64]
     lib.cc_layernorm_bf16.argtypes = [
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
         c.c_float, c.c_uint64]
@@ -808,6 +822,60 @@ def attn_pool(x, u_hi, u_lo, usum, n: int, seq: int, heads: int, *,
         u_hi.data_ptr(), u_lo.data_ptr(),
         0 if shared else ATTN_POOL_HEADS * hidden, usum.data_ptr(),
         out.data_ptr(), n, seq, heads, hidden, splits,
+        ws.data_ptr() if ws is not None else None, plan.workspace_floats,
+        stream))
+    return out
+
+
+def attn_cross_plan(n: int, nq: int, nk: int, heads: int, hidden: int,
+                    splits: int = 0) -> AttnCrossPlan:
+    """The launch plan of a cc_attn_cross call with these arguments
+    (cc_attn_cross_plan; host-only).  ``splits`` 0 asks for the plan's own
+    choice; a forced value comes back clamped so that no split is empty.
+    Raises on arguments cc_attn_cross itself would reject."""
+    plan = AttnCrossPlan()
+    check(load().cc_attn_cross_plan(n, nq, nk, heads, hidden, splits,
+                                    ctypes.byref(plan)))
+    return plan
+
+
+@functools.lru_cache(maxsize=None)
+def attn_cross_supported(heads: int, hidden: int) -> bool:
+    """Whether cc_attn_cross takes this head geometry — the library's own
+    answer (csrc/cc_attncross_plan.hpp).  Asked once per geometry."""
+    return bool(load().cc_attn_cross_supported(heads, hidden))
+
+
+def attn_cross(q, kv, n: int, nq: int, nk: int, heads: int, *,
+               scale: float | None = None, splits: int = 0):
+    """Cross-attention of ``nq`` <= 32 queries per clip over ``nk`` keys on
+    the device (cc_attn_cross): softmax(Q K^T scale) V, bf16 [n*nq, H].
+
+    ``q`` bf16 [n*nq, H] and ``kv`` bf16 [n*nk, 2H] (K section, then V
+    section, heads inside each); the rows of both may be strided, so ``kv``
+    may be a column window of a wider GEMM output.  ``scale`` defaults to
+    head_dim ** -0.5.  No fallback: a failing call raises."""
+    import torch
+
+    lib = require_gpu()
+    hidden = q.shape[1] if q.dim() == 2 else -1
+    for name, t, rows, cols in (("q", q, n * nq, hidden), ("kv", kv, n * nk, 2 * hidden)):
+        if (t.dim() != 2 or tuple(t.shape) != (rows, cols)
+                or t.dtype != torch.bfloat16 or not t.is_cuda or t.stride(1) != 1
+                or (rows > 1 and t.stride(0) < cols)):
+            raise ValueError(
+                f"{name} must be a ({rows}, {cols}) bf16 device tensor with "
+                f"unit column stride and rows that do not overlap")
+    plan = attn_cross_plan(n, nq, nk, heads, hidden, splits)
+    out = torch.empty((n * nq, hidden), dtype=torch.bfloat16, device=q.device)
+    ws = (torch.empty(plan.workspace_floats, dtype=torch.float32, device=q.device)
+          if plan.workspace_floats else None)
+    stream = torch.cuda.current_stream(q.device).cuda_stream
+    check(lib.cc_attn_cross(
+        q.data_ptr(), q.stride(0) if n * nq > 1 else hidden,
+        kv.data_ptr(), kv.stride(0) if n * nk > 1 else 2 * hidden,
+        out.data_ptr(), n, nq, nk, heads, hidden,
+        (hidden // heads) ** -0.5 if scale is None else scale, splits,
         ws.data_ptr() if ws is not None else None, plan.workspace_floats,
         stream))
     return out

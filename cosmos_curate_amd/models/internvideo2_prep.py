@@ -2,8 +2,9 @@
 
 The exact PREPROCESSING math the InternVideo2 / Cosmos-Embed1 stages feed
 their networks with.  The InternVideo2 tower that consumes it is
-models/internvideo2_vit.py (through models/internvideo2.py); Cosmos-Embed1
-has no tower here.
+models/internvideo2_vit.py (through models/internvideo2.py), the
+Cosmos-Embed1 tower models/cosmos_embed1_vit.py (through
+models/cosmos_embed1.py, with its config's mean / std).
 
 - ``formulate_input_frames`` mirrors internvideo2_mm.py:391-438
   ``_construct_frames``: temporal subsample step = len//fnum then [:fnum],
@@ -45,11 +46,14 @@ def temporal_subsample(n_frames: int, fnum: int) -> npt.NDArray[np.int64]:
 
 @torch.no_grad()
 def formulate_input_frames(
-    frames_u8_dev: torch.Tensor, fnum: int = 8, target_size: int = 224
+    frames_u8_dev: torch.Tensor, fnum: int = 8, target_size: int = 224,
+    mean: tuple[float, float, float] = IV2_MEAN,
+    std: tuple[float, float, float] = IV2_STD,
 ) -> torch.Tensor:
     """(T,H,W,3) u8 CUDA tensor -> (1, fnum, 3, size, size) f32 CUDA.
 
-    The device mirror of internvideo2_mm.formulate_input_frames (:426-438).
+    The device mirror of internvideo2_mm.formulate_input_frames (:426-438);
+    ``mean`` / ``std`` default to its constants.
     """
     lib = hotpath.require_gpu()
     assert frames_u8_dev.is_cuda and frames_u8_dev.dtype == torch.uint8
@@ -74,11 +78,11 @@ def formulate_input_frames(
         (fnum, 3, target_size, target_size), dtype=torch.float32,
         device=frames_u8_dev.device,
     )
-    mean = (ctypes.c_float * 3)(*IV2_MEAN)
-    std = (ctypes.c_float * 3)(*IV2_STD)
+    mean_c = (ctypes.c_float * 3)(*mean)
+    std_c = (ctypes.c_float * 3)(*std)
     hotpath.check(
         lib.cc_clip_preprocess(
-            resized.data_ptr(), fnum, target_size, target_size, mean, std,
+            resized.data_ptr(), fnum, target_size, target_size, mean_c, std_c,
             out.data_ptr(), 0, stream,
         )
     )

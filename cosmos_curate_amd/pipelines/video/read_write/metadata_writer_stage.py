@@ -9,7 +9,9 @@ clip payloads + per-clip metadata + embeddings parquet + summary.json):
     <output>/clips/<uuid>.bin              clip payload (mp4 or raw-NV12)
     <output>/metas/v0/<uuid>.json          span, source, errors
     <output>/clip_embd/chunk_<i>.parquet   id + embedding (pyarrow);
-                                           iv2_embd/ under internvideo2
+                                           iv2_embd/ under internvideo2,
+                                           ce1_embd_<variant>/ under
+                                           cosmos-embed1-<variant>
     <output>/summary.json                  counts + clips/sec + stage perf
 
 The output tree names follow the reference's helpers (:167-223:
@@ -33,12 +35,17 @@ from cosmos_curate_amd.core.utils.performance_utils import StageTimer, summarize
 from cosmos_curate_amd.pipelines.video.utils.data_model import SplitPipeTask
 
 
+COSMOS_EMBED1_PREFIX = "cosmos-embed1-"  # + 224p | 336p | 448p
+
+
 def embd_stem(embedding_algorithm: str) -> str:
     """Directory of the embeddings parquet (metadata_writer_stage.py:226-235
-    ``_embd_stem``): ``iv2_embd`` for InternVideo2, ``<algorithm>_embd``
-    otherwise."""
+    ``_embd_stem``): ``iv2_embd`` for InternVideo2, ``ce1_embd_<variant>``
+    for ``cosmos-embed1-<variant>``, ``<algorithm>_embd`` otherwise."""
     if embedding_algorithm == "internvideo2":
         return "iv2_embd"
+    if embedding_algorithm.startswith(COSMOS_EMBED1_PREFIX):
+        return "ce1_embd_" + embedding_algorithm.removeprefix(COSMOS_EMBED1_PREFIX)
     return f"{embedding_algorithm}_embd"
 
 
@@ -46,6 +53,8 @@ def clip_embedding_of(clip, embedding_algorithm: str):
     """The embedding the run's algorithm produced on this clip, or None."""
     if embedding_algorithm == "internvideo2":
         return clip.intern_video_2_embedding
+    if embedding_algorithm.startswith(COSMOS_EMBED1_PREFIX):
+        return clip.cosmos_embed1_embedding
     return clip.clip_embedding
 
 

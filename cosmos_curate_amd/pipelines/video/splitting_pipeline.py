@@ -18,6 +18,9 @@ Stage order (reference _assemble_stages):
       or, under --embedding-algorithm internvideo2:
     InternVideo2FrameCreationStage
     InternVideo2EmbeddingStage      (video tower, MFMA path)
+      or, under --embedding-algorithm cosmos-embed1-224p|336p|448p:
+    CosmosEmbed1FrameCreationStage
+    CosmosEmbed1EmbeddingStage      (video tower + Q-Former, MFMA path)
     ClipWriterStage
 """
 
@@ -51,6 +54,7 @@ from cosmos_curate_amd.pipelines.video.embedding.clip_stages import (
 )
 from cosmos_curate_amd.pipelines.video.read_write.download_stages import VideoDownloader
 from cosmos_curate_amd.pipelines.video.read_write.metadata_writer_stage import (
+    COSMOS_EMBED1_PREFIX,
     ClipWriterStage,
     write_split_summary,
 )
@@ -58,6 +62,8 @@ from cosmos_curate_amd.pipelines.video.utils.data_model import SplitPipeTask, Vi
 from cosmos_curate_amd.pipelines.video.utils.decoder_utils import FrameExtractionPolicy
 
 VIDEO_SUFFIXES = {".mp4", ".mov", ".mkv", ".nv12", ".bin"}
+COSMOS_EMBED1_ALGORITHMS = tuple(
+    COSMOS_EMBED1_PREFIX + v for v in ("224p", "336p", "448p"))
 
 
 def extract_multi_cam_split_tasks(
@@ -223,6 +229,7 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
             log_stats=True,
         ))
     iv2 = args.embedding_algorithm == "internvideo2"
+    ce1 = args.embedding_algorithm in COSMOS_EMBED1_ALGORITHMS
     if args.generate_embeddings and iv2:
         from cosmos_curate_amd.pipelines.video.embedding.internvideo2_stages import (
             InternVideo2EmbeddingStage,
@@ -235,6 +242,16 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
         stages.append(
             InternVideo2EmbeddingStage.with_pool_head(pool["pool_head"], log_stats=True)
             if pool else InternVideo2EmbeddingStage(log_stats=True))
+    elif args.generate_embeddings and ce1:
+        from cosmos_curate_amd.pipelines.video.embedding.cosmos_embed1_stages import (
+            CosmosEmbed1EmbeddingStage,
+            CosmosEmbed1FrameCreationStage,
+        )
+
+        variant = args.embedding_algorithm.removeprefix(COSMOS_EMBED1_PREFIX)
+        stages.append(CosmosEmbed1FrameCreationStage(
+            variant, target_fps=args.target_clip_fps, log_stats=True))
+        stages.append(CosmosEmbed1EmbeddingStage(variant, log_stats=True))
     elif args.generate_embeddings:
         res = args.clip_extraction_target_res
         stages.append(ClipFrameCreationStage(
@@ -247,7 +264,7 @@ def _assemble_stages(args: argparse.Namespace) -> list[CuratorStage | CuratorSta
             **_pool_kw(args)))
     stages.append(ClipWriterStage(
         args.output_clip_path, log_stats=True,
-        **({"embedding_algorithm": "internvideo2"} if iv2 else {})))
+        **({"embedding_algorithm": args.embedding_algorithm} if iv2 or ce1 else {})))
     return stages
 
 
@@ -299,8 +316,12 @@ def _setup_parser(parser: argparse.ArgumentParser) -> None:
     parser.add_argument("--embedding-algorithm", default="clip",
                         help="internvideo2 embeds each clip with the "
                         "InternVideo2 video tower (512 wide, written under "
-                        "iv2_embd/); any other value names the run and "
-                        "embeds with the --embedding-model image tower")
+                        "iv2_embd/); cosmos-embed1-224p|336p|448p embeds it "
+                        "with the Cosmos-Embed1 video tower at that input "
+                        "resolution (256 wide at 224p, else 768, written "
+                        "under ce1_embd_<variant>/); any other value names "
+                        "the run and embeds with the --embedding-model image "
+                        "tower")
     parser.add_argument("--embedding-model", default="vit_b32",
                         choices=sorted(EMBEDDING_MODELS),
                         help="vision tower of the embedding stage "

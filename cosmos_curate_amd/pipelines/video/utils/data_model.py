@@ -97,6 +97,9 @@ class Clip:
     # over a (1, T, 3, H, W) f32 device tensor) and the video embedding
     intern_video_2_frames: LazyData | None = None
     intern_video_2_embedding: npt.NDArray[np.float32] | None = None
+    # Cosmos-Embed1 (data_model.py:233-234): the same pair, T = 8
+    cosmos_embed1_frames: LazyData | None = None
+    cosmos_embed1_embedding: npt.NDArray[np.float32] | None = None
     # aesthetic filter (data_model.py:241)
     aesthetic_score: float | None = None
     # motion filter (data_model.py:236-239)

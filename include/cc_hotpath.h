@@ -493,6 +493,41 @@ int cc_attn_pool(const void* x, int64_t ldx, const float* murstd,
                  int H, int splits, float* workspace, int64_t workspace_floats,
                  uint64_t stream);
 
+/* ---- few-query cross-attention (the Q-Former of the Cosmos-Embed1 tower;
+ * DESIGN.md §29).  out[n, nq, H] = softmax(Q K^T * scale) V per (clip, head):
+ * replaces the torch.nn.functional.scaled_dot_product_attention call, and the
+ * three permutes around it, that a BERT-style cross-attention layer
+ * (transformers' Blip2QFormerMultiHeadAttention) makes with nq queries against
+ * nk encoder tokens.  All bf16: q row i of clip f at q + (f*nq + i)*ldq; kv row
+ * t of clip f at kv + (f*nk + t)*ldkv, holding the K section [0, H) then the V
+ * section [H, 2H), heads inside each — the output of one GEMM against
+ * [Wk; Wv], or a column window of a wider one (ldkv >= 2H free); out
+ * [n*nq, H] dense.  No mask.  Head dim 64 only (H == 64*heads), 1 <= nq <= 32,
+ * nk >= 1, else CC_ERR_UNSUPPORTED.  splits 0 = the plan's choice, a forced
+ * value is clamped so that no split is empty; with more than one split the
+ * f32 partials go through `workspace` (at least cc_attn_cross_plan's
+ * workspace_floats elements, else may be null) and a second kernel adds them
+ * in split order.  No atomics: bit-identical from run to run.  Timed as
+ * "attn_cross" (and "attn_cross_combine").  CC_ERR_INVALID on null or
+ * misaligned (16 bytes) pointers, non-positive n/nq/nk, ldq < H, ldkv < 2H,
+ * an ld that is no multiple of 8 or a workspace too small — all before any
+ * launch. */
+typedef struct cc_attn_cross_plan_info {
+  int32_t splits;            /* workgroups per (clip, head) */
+  int32_t chunk;             /* keys per MFMA tile */
+  int32_t chunks_per_split;  /* a split's keys = chunk * this */
+  int32_t grid;              /* workgroups launched (n * heads * splits) */
+  int32_t block;             /* threads per workgroup */
+  int64_t workspace_floats;  /* f32 elements of workspace (0 at splits 1) */
+} cc_attn_cross_plan_info;
+int cc_attn_cross_plan(int64_t n, int nq, int nk, int heads, int hidden,
+                       int splits, cc_attn_cross_plan_info* out);
+int cc_attn_cross_supported(int heads, int hidden); /* 1 or 0; host-only */
+int cc_attn_cross(const void* q, int64_t ldq, const void* kv, int64_t ldkv,
+                  void* out, int64_t n, int nq, int nk, int heads, int hidden,
+                  float scale, int splits, float* workspace,
+                  int64_t workspace_floats, uint64_t stream);
+
 /* ---- fused bf16 LayerNorm (replaces torch layer_norm in the ViT
  * forward; f32 stats/affine; H = 128, 1152, 1408 or one of the
  * instantiated multiples of 256: 256, 512, 768, 1024, 2048, 3072, 4096). */
